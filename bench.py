@@ -26,6 +26,10 @@ results + speaker embeddings are gathered and merged in file order on rank 0 (ov
 speakers).  Weak scaling: every GPU holds ~--seconds of the file.
 
 Run:  python bench.py [--gpus N --steps K --warmup W]   (N>1 via torch.distributed.run)
+A plain run sets up, warms up, times the K steps and prints the line (the live kernel clock
+samples inside the timed steps).  --full adds the legs with runs of their own: the beam-5
+sub-record (`beam5`) and the CPU baseline (`cpu_baseline`); both are null without it.
+--dump-outputs DIR writes the last timed step's results as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -77,6 +81,13 @@ def parse():
                     help="N=1 greedy runs: also time the reference's default decode (beam search, 5 beams, "
                          "src/transcribe.rs:22-33) over the first this-many seconds of the shard (0: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the beam-5 "
+                         "sub-record (--beam-seconds) and the CPU baseline (--cpu-audio; --no-cpu-baseline "
+                         "drops it).  A plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "segments, words, their texts and speakers, the segmentation stage's speech spans")
     ap.add_argument("--keepalive", type=int, default=0,
                     help="A/B diagnostic: a host thread keeps a low-priority stream busy with 1-workgroup "
                          "spin kernels of this many cycles during the timed steps (0: off)")
@@ -354,6 +365,34 @@ def beam5_record(ctx, dia, vad, pcm, segs, opts, dopts, diarize, args):
             "note": "same context, weights and pins as the main line; the first %.0f s of its shard" % audio}
 
 
+def dump_outputs(path, segments, spans=None):
+    """--dump-outputs: the last timed step's return value as arrays, one DIR/<name>.npy each
+    (float64; 1 h of audio is a few hundred KB in all, so everything is written, nothing sampled).
+      segments      [n, 3]   start s, end s, number of words of every output Segment
+      words         [m, 4]   index of its segment, start s, end s, probability (NaN: none)
+      segment_text  [..]     the segments' texts as Unicode code points, one '\\n' after each
+      word_text     [..]     the words' texts, the same way
+      speakers      [..]     the segments' speaker ids, the same way (empty line: none)
+      speech_spans  [k, 2]   start s, end s of the segmentation stage's speech spans
+                             (one-process runs: the stage's own result, not the pinned spurts)"""
+    import numpy as np
+
+    def codes(strs):
+        return np.array([ord(ch) for s in strs for ch in (s or "") + "\n"], np.float64)
+    os.makedirs(path, exist_ok=True)
+    words = [(i, w.start, w.end, np.nan if w.probability is None else w.probability)
+             for i, s in enumerate(segments) for w in (s.words or [])]
+    arrs = {"segments": np.array([(s.start, s.end, len(s.words or [])) for s in segments], np.float64).reshape(-1, 3),
+            "words": np.array(words, np.float64).reshape(-1, 4),
+            "segment_text": codes([s.text for s in segments]),
+            "word_text": codes([w.text for s in segments for w in (s.words or [])]),
+            "speakers": codes([s.speaker_id for s in segments])}
+    if spans is not None:
+        arrs["speech_spans"] = np.array([(a, b) for a, b in spans], np.float64).reshape(-1, 2)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main_inproc(args):
     """--multi inproc: ONE process, N GPUs, libwdr's own multi-GPU path (gpu_device = None,
     WDR_DEVICES = 0..N-1 unless set; decode chains spread over the GPUs, chain k on GPU k % N,
@@ -435,6 +474,8 @@ def main_inproc(args):
         out, _ = step()
         n_out += len(out)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     times = ctx.stage_times()
     shard_s = pcm.size / 16000.0
     line = {
@@ -542,13 +583,14 @@ def main():
             vad_t[0] += time.perf_counter() - t
             vad_t[1] = segs_n
             return res if res is not None else ([], None)
-        segs = None
+        segs = spans = None
     else:
         pcm, spurts = synth_speech(args.seconds, seed=rank, n_speakers=args.speakers or (3 if diarize else 1))
         segs = [wdr.SpeechSegment(a, b, pcm[int(round(a * 16000)):int(round(b * 16000))]) for a, b, _ in spurts]
         audio_s = float(sum(s.samples.size for s in segs)) / 16000.0   # speech seconds handed to the pipeline
         shard_s = pcm.size / 16000.0                                  # wall-clock audio covered (xRT basis)
         segs_n = len(segs)
+        spans = []   # the segmentation stage's (start, end) pairs of the latest step
 
         def step():
             # the segmentation stage over the whole shard runs and is timed; in synthetic mode the
@@ -556,11 +598,11 @@ def main():
             # (BASELINE.md §2 pin)
             t = time.perf_counter()
             if diarize:   # libwdr makes every segment's samples; the Python copy of them is skipped
-                n_seg = len(dia.get_segments(pcm, materialize=False))
+                spans[:] = dia.get_segments(pcm, materialize=False)
             else:
-                n_seg = len(vad.get_segments(pcm, materialize=False)[1])
+                spans[:] = vad.get_segments(pcm, materialize=False)[1]
             vad_t[0] += time.perf_counter() - t
-            vad_t[1] = n_seg
+            vad_t[1] = len(spans)
             return ctx.run_pipeline(segs, opts, diarize_options=dopts)
 
     if args.keepalive > 0 or args.keepalive_mb > 0:
@@ -735,12 +777,16 @@ def main():
 
     pipe = pipeline_roofline(args.model, times, dt / args.steps)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, spans)
+
+    # the legs with runs of their own (--full)
     beam = None
-    if rank == 0 and world == 1 and args.strategy == "greedy" and args.beam_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.strategy == "greedy" and args.beam_seconds > 0:
         beam = beam5_record(ctx, dia, vad, pcm, segs, opts, dopts, diarize, args)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ctx.close()
         res, sample, tmax = cpu_baseline(args.model, segs, args.cpu_audio)
         # the faster of the thread counts tried (oversubscribed BLAS pools on a many-core host can

@@ -24,6 +24,6 @@ python3 tools/busy.py $(find $O/trace -name "*kernel_trace.csv" | head -1) 0.1 >
 python3 tools/prof_summary.py $O/trace --fetch $O/fetch --write $O/write --drop-trace --json $O/pmc.json > $O/summary.txt
 rm -f $O/fetch/*/*counter_collection.csv.big 2>/dev/null || true
 unset WDR_LAUNCH_LOCK WDR_NO_GRAPH
-timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cat $O/summary.txt | head -60
 cat $O/bench_default.json

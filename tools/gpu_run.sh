@@ -10,7 +10,7 @@
 #   configs     pytest tests/test_gpu_configs.py (C2 / C3 / C4-shard fixtures)
 #   suite       the whole -m gpu suite
 #   smoke       __graft_entry__.smoke()
-#   bench       python bench.py (default line) -> gpurun_out/bench.json
+#   bench       python bench.py --full (default line + the beam-5 and CPU-baseline legs) -> bench.json
 #   benchfast   python bench.py without the beam-5 and CPU-baseline legs -> gpurun_out/bench_fast.json
 #   bench8      the same with --fp8 (configs[4] encoder)
 #   xattn       tools/xattn_bench (cross-attention partial + combine by row count), then its
@@ -20,6 +20,7 @@
 # TAG=name: suffix of the output files (A/B runs of one step under different env knobs) -> gpurun_out/bench_fp8.json
 set -e -o pipefail
 mkdir -p gpurun_out
+OUT=$_   # the output folder made above
 export LD_LIBRARY_PATH=$PWD/whisper-diarize-rs_amd:$LD_LIBRARY_PATH
 PYT="python3 -u -m pytest -x -q --timeout 400 --timeout-method thread -m gpu"
 T=${TAG:+_$TAG}
@@ -34,7 +35,7 @@ for step in "$@"; do
     configs) timeout -k 10 1100 $PYT -s tests/test_gpu_configs.py > gpurun_out/configs.log 2>&1 || { tail -40 gpurun_out/configs.log; exit 1; }; tail -8 gpurun_out/configs.log ;;
     suite) timeout -k 10 1150 python3 -u -m pytest tests -m gpu -x -q --timeout 400 --timeout-method thread --durations 15 > gpurun_out/suite.log 2>&1 || { tail -60 gpurun_out/suite.log; exit 1; }; tail -22 gpurun_out/suite.log ;;
     smoke) timeout -k 10 150 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/smoke.log 2>&1; tail -1 gpurun_out/smoke.log ;;
-    bench) timeout -k 10 600 python3 bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; cat gpurun_out/bench.json ;;
+    bench) timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json ;;
     benchfast) timeout -k 10 400 python3 bench.py --beam-seconds 0 --no-cpu-baseline > gpurun_out/bench_fast$T.json 2> gpurun_out/bench_fast$T.err; python3 tools/bench_brief.py gpurun_out/bench_fast$T.json ;;
     bench8) timeout -k 10 400 python3 bench.py --fp8 --beam-seconds 0 --no-cpu-baseline > gpurun_out/bench_fp8$T.json 2> gpurun_out/bench_fp8$T.err; python3 tools/bench_brief.py gpurun_out/bench_fp8$T.json ;;
     xattn) timeout -k 10 120 ./tools/xattn_bench > gpurun_out/xattn$T.log 2>&1; cat gpurun_out/xattn$T.log
