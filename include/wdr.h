@@ -282,6 +282,13 @@ void wdr_context_free(wdr_context* c);
  * n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer, n_text_ctx, n_text_state, n_text_head,
  * n_text_layer, n_mels, ftype; wdr_context_create loads such a file when model_path is given */
 int wdr_ggml_info(const char* path, int32_t* hparams, int64_t* n_tensors, int64_t* n_vocab_tokens);
+/* Tensor types of such a file (no GPU): counts[16], the number of tensors per ggml type id.  The
+ * loader reads 0 f32, 1 f16 and the block-quantized 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0 (the
+ * files of whisper.cpp's quantize tool; ftype = base + 1000 * qnt_version); other ids fail. */
+int wdr_ggml_tensor_types(const char* path, int64_t* counts /* [16] */);
+/* one tensor of such a file as f16 bits (no GPU), quantized types through the host definition:
+ * float(d) * q (+ float(m)) in f32, rounded once to f16.  Free *out with wdr_free. */
+int wdr_ggml_tensor_f16(const char* path, const char* name, uint16_t** out, size_t* n);
 /* diarize: NULL = no speakers (the reference's `None`); else speaker embeddings of every speech
  * segment + EmbeddingManager assignment per whisper segment */
 int wdr_run_pipeline(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs, const wdr_transcribe_options* opts,
@@ -361,6 +368,10 @@ void wdr_result_free(wdr_result_seg* segs, size_t n);
 /* ---- kernel-level test seams (host buffers in / out) ---- */
 int wdr_dbg_log_mel(wdr_context* c, const float* x, size_t n, int32_t seek, float* window_out /* [n_mels][3000] */);
 int wdr_dbg_energy(const float* x, size_t n, float* out);
+/* the load-time dequantization kernel: n_blocks raw blocks of ggml type 2 / 3 / 6 / 7 / 8 ->
+ * out_f16[32 * n_blocks] (f16 bits), bit-identical to wdr_ggml_tensor_f16's host definition; ms
+ * (nullable): mean GPU time of 10 further back-to-back launches on the same buffers */
+int wdr_dbg_dequant(int32_t type, const uint8_t* blocks, size_t n_blocks, uint16_t* out_f16, double* ms);
 /* one v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3) on raw per-lane operands: a / b [64 lanes][32 B],
  * scale registers sa / sb [64] (op_sel 0), out [64 lanes][4] accumulators */
 int wdr_dbg_mfma_scale(const uint8_t* a, const uint8_t* b, const int32_t* sa, const int32_t* sb, float* out);

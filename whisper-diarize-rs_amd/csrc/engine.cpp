@@ -1924,6 +1924,59 @@ int wdr_ggml_info(const char* path, int32_t* hparams, int64_t* n_tensors, int64_
   })
 }
 
+int wdr_ggml_tensor_types(const char* path, int64_t* counts) {
+  WDR_GUARD({
+    if (!path || !file_exists(path)) return fail("whisper file doesn't exist");
+    const GgmlFile f(path);
+    for (int i = 0; i < 16; ++i) counts[i] = 0;
+    for (const auto& kv : f.tensors) ++counts[kv.second.type];   // the reader admits ids 0..8 only
+    return 0;
+  })
+}
+
+int wdr_ggml_tensor_f16(const char* path, const char* name, uint16_t** out, size_t* n) {
+  WDR_GUARD({
+    if (!path || !file_exists(path)) return fail("whisper file doesn't exist");
+    if (!name) return fail("tensor name missing");
+    const GgmlFile f(path);
+    const std::vector<uint16_t> v = f.as_f16(name, f.get(name).n_elem());
+    *out = (uint16_t*)malloc(std::max<size_t>(1, v.size()) * 2);
+    if (!v.empty()) memcpy(*out, v.data(), v.size() * 2);
+    *n = v.size();
+    return 0;
+  })
+}
+
+int wdr_dbg_dequant(int32_t type, const uint8_t* blocks, size_t n_blocks, uint16_t* out_f16, double* ms) {
+  WDR_GUARD({
+    const int bs = ggml_block_bytes(type);
+    if (!bs) return fail("dequant: type must be 2 (q4_0), 3 (q4_1), 6 (q5_0), 7 (q5_1) or 8 (q8_0)");
+    if (!n_blocks) return 0;
+    // the source padded to a dword, as the loader's staging buffer is
+    DevMem in((n_blocks * bs + 3) & ~size_t(3)), out(n_blocks * 64);
+    WDR_HIP(hipMemcpy(in.p, blocks, n_blocks * bs, hipMemcpyHostToDevice));
+    launch_dequant(type, in.p, (long long)n_blocks, out.as<f16>(), nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    if (ms) {   // mean of 10 more launches of the same buffers, back to back, between two events
+      const int reps = 10;
+      hipEvent_t e0, e1;
+      WDR_HIP(hipEventCreate(&e0));
+      WDR_HIP(hipEventCreate(&e1));
+      WDR_HIP(hipEventRecord(e0, nullptr));
+      for (int i = 0; i < reps; ++i) launch_dequant(type, in.p, (long long)n_blocks, out.as<f16>(), nullptr);
+      WDR_HIP(hipEventRecord(e1, nullptr));
+      WDR_HIP(hipEventSynchronize(e1));
+      float t = 0.f;
+      WDR_HIP(hipEventElapsedTime(&t, e0, e1));
+      WDR_HIP(hipEventDestroy(e0));
+      WDR_HIP(hipEventDestroy(e1));
+      *ms = (double)t / reps;
+    }
+    WDR_HIP(hipMemcpy(out_f16, out.p, n_blocks * 64, hipMemcpyDeviceToHost));
+    return 0;
+  })
+}
+
 int wdr_run_pipeline(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs, const wdr_transcribe_options* o,
                      const wdr_diarize_options* dopts, const wdr_synthetic* syn, const wdr_callbacks* cb,
                      wdr_segment_list** out) {

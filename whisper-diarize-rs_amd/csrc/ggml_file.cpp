@@ -63,6 +63,12 @@ uint16_t f2h(float f) {
   return (uint16_t)(s | r);
 }
 
+uint16_t ld16(const char* p) {
+  uint16_t v;
+  memcpy(&v, p, 2);
+  return v;
+}
+
 struct Reader {
   const char* p;
   const char* end;
@@ -83,6 +89,31 @@ struct Reader {
 };
 
 }  // namespace
+
+void ggml_dequant_f32(int type, const char* blocks, int64_t n_blocks, float* out) {
+  const int bs = ggml_block_bytes(type);
+  if (!bs) bad("unsupported tensor type " + std::to_string(type));
+  const bool has_m = type == 3 || type == 7, has_qh = type == 6 || type == 7;
+  for (int64_t b = 0; b < n_blocks; ++b, blocks += bs, out += 32) {
+    const float d = h2f(ld16(blocks));
+    const float m = has_m ? h2f(ld16(blocks + 2)) : 0.f;
+    if (type == 8) {
+      for (int i = 0; i < 32; ++i) out[i] = d * (float)(int8_t)blocks[2 + i];
+      continue;
+    }
+    uint32_t qh = 0;
+    if (has_qh) memcpy(&qh, blocks + (has_m ? 4 : 2), 4);
+    const uint8_t* qs = (const uint8_t*)blocks + (bs - 16);
+    // q4_0 / q5_0 are centred (-8 / -16), q4_1 / q5_1 carry the minimum m instead
+    const int sub = type == 2 ? 8 : type == 6 ? 16 : 0;
+    for (int e = 0; e < 32; ++e) {
+      const int nib = e < 16 ? qs[e] & 15 : qs[e - 16] >> 4;
+      const int q = (nib | (int)((qh >> e) & 1) << 4) - sub;
+      const float v = d * (float)q;   // exact in f32
+      out[e] = has_m ? v + m : v;
+    }
+  }
+}
 
 GgmlFile::GgmlFile(const std::string& path) {
   const int fd = open(path.c_str(), O_RDONLY);
@@ -118,12 +149,15 @@ GgmlFile::GgmlFile(const std::string& path) {
   while (r.p < r.end) {
     const int32_t nd = r.get<int32_t>(), nl = r.get<int32_t>(), type = r.get<int32_t>();
     if (nd < 1 || nd > 4 || nl <= 0 || nl > 1024) bad("bad tensor header");
-    if (type != 0 && type != 1) bad("unsupported tensor type " + std::to_string(type) + " (only f32 / f16 models)");
+    if (type != 0 && type != 1 && !ggml_block_bytes(type))
+      bad("unsupported tensor type " + std::to_string(type) + " (supported: f32, f16, q4_0, q4_1, q5_0, q5_1, q8_0)");
     GgmlTensor t;
     t.type = type;
     for (int i = 0; i < nd; ++i) t.ne.push_back(r.get<int32_t>());
     const std::string name(r.take(nl), nl);
-    t.data = r.take((size_t)t.n_elem() * (type == 0 ? 4 : 2));
+    if (t.quantized() && t.ne[0] % 32 != 0)
+      bad("quantized tensor '" + name + "' has ne[0] = " + std::to_string(t.ne[0]) + ", not a multiple of 32");
+    t.data = r.take(t.n_bytes());
     tensors[name] = t;
   }
 }
@@ -145,6 +179,8 @@ std::vector<float> GgmlFile::as_f32(const std::string& name, int64_t n) const {
   std::vector<float> out((size_t)n);
   if (t.type == 0) {
     memcpy(out.data(), t.data, (size_t)n * 4);
+  } else if (t.quantized()) {
+    ggml_dequant_f32(t.type, t.data, n / 32, out.data());
   } else {
     for (int64_t i = 0; i < n; ++i) {
       uint16_t h;
@@ -162,6 +198,10 @@ std::vector<uint16_t> GgmlFile::as_f16(const std::string& name, int64_t n) const
   std::vector<uint16_t> out((size_t)n);
   if (t.type == 1) {
     memcpy(out.data(), t.data, (size_t)n * 2);
+  } else if (t.quantized()) {
+    std::vector<float> v((size_t)n);
+    ggml_dequant_f32(t.type, t.data, n / 32, v.data());
+    for (int64_t i = 0; i < n; ++i) out[i] = f2h(v[i]);
   } else {
     for (int64_t i = 0; i < n; ++i) {
       float f;

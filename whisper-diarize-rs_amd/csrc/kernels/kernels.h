@@ -33,6 +33,10 @@ void launch_energy(const float* x, int n, float* e, hipStream_t s);
 void launch_i16_to_f32(const int16_t* in, int n, float* out, hipStream_t s);
 void launch_synth_fill(void* dst, long long rows, int src_cols, int dst_cols, uint64_t seed, float scale, bool f16out,
                        int mode, float cval, hipStream_t s);
+// kernels/quant.hip: n_blocks raw blocks of a quantized ggml type (2 / 3 / 6 / 7 / 8, ggml_file.h)
+// -> 32 * n_blocks f16.  blocks and dst 16-byte aligned; the source is read up to its size rounded
+// up to a dword, so the caller pads its buffer that far
+void launch_dequant(int type, const void* blocks, long long n_blocks, f16* dst, hipStream_t s);
 void launch_layernorm(const float* x, int ldx, const float* g, const float* b, f16* y, int ldy, int rows, int d,
                       hipStream_t s);
 void launch_embed(const f16* E, const float* P, const int* tok, const int* pos, int R, int d, float* x, hipStream_t s);

@@ -496,12 +496,33 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
   // hash).  Both paths name every tensor as whisper.cpp does.
   hipStream_t s = stream;
   const double sq3 = std::sqrt(3.0);
+  // block-quantized tensors (q4_0 .. q8_0) bound for an f16 buffer: the raw blocks go to one
+  // staging buffer (sized for the file's largest such tensor, padded to a dword for the kernel's
+  // last read) and are dequantized there on the GPU; released when the load is done
+  DevMem qstage;
+  if (gf) {
+    size_t mx = 0;
+    for (const auto& kv : gf->tensors)
+      if (kv.second.quantized()) mx = std::max(mx, kv.second.n_bytes());
+    if (mx) qstage = DevMem((mx + 3) & ~size_t(3));
+  }
   auto fill = [&](void* dst, const std::string& nm, long long rows, int src_cols, int dst_cols, bool is16, double sd) {
     if (!gf) {
       launch_synth_fill(dst, rows, src_cols, dst_cols, fnv1a64(nm), (float)(sd * sq3), is16, 0, 0.f, s);
       return;
     }
     const int64_t n = rows * (int64_t)src_cols;
+    if (is16 && gf->get(nm).quantized()) {
+      const GgmlTensor& t = gf->get(nm);
+      WDR_CHECK(t.n_elem() == n, "failed to open model: tensor '" + nm + "' has " + std::to_string(t.n_elem()) +
+                                     " elements, expected " + std::to_string(n));
+      WDR_CHECK(dst_cols == src_cols, "ggml load: padded quantized tensor '" + nm + "'");
+      WDR_CHECK(t.n_bytes() <= qstage.bytes, "ggml load: quantized staging buffer too small");
+      WDR_HIP(hipMemcpy(qstage.p, t.data, t.n_bytes(), hipMemcpyHostToDevice));
+      launch_dequant(t.type, qstage.p, n / 32, (f16*)dst, s);
+      WDR_HIP(hipStreamSynchronize(s));   // the next tensor overwrites the staging buffer
+      return;
+    }
     if (is16) {
       std::vector<uint16_t> v = gf->as_f16(nm, n), padded;
       if (dst_cols != src_cols) {
@@ -617,6 +638,7 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
     if (!flat.empty()) WDR_HIP(wdr_memcpy_async(aheads_dev.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice, s));
   }
   WDR_HIP(hipStreamSynchronize(s));
+  qstage = DevMem();
   {
     // KV pool for the decode chains of every State of this context (multi-chain pipeline)
     const char* e = getenv("WDR_DECODE_CHAINS");

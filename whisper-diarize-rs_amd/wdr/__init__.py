@@ -545,7 +545,48 @@ def ggml_info(path: str) -> dict:
     L.check(lib.wdr_ggml_info(path.encode(), hp, C.byref(nt), C.byref(nv)))
     keys = ["n_vocab", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer", "n_text_ctx",
             "n_text_state", "n_text_head", "n_text_layer", "n_mels", "ftype"]
-    return {**dict(zip(keys, list(hp))), "n_tensors": nt.value, "n_vocab_tokens": nv.value}
+    counts = (C.c_int64 * 16)()
+    L.check(lib.wdr_ggml_tensor_types(path.encode(), counts))
+    ftype = hp[10]
+    return {**dict(zip(keys, list(hp))), "n_tensors": nt.value, "n_vocab_tokens": nv.value,
+            # quantized files (whisper.cpp's quantize tool): ftype = base + 1000 * qnt_version
+            "ftype_base": ftype % 1000, "qnt_version": ftype // 1000,
+            "tensor_types": {i: int(c) for i, c in enumerate(counts) if c}}
+
+
+GGML_QUANT_TYPES = {"q4_0": 2, "q4_1": 3, "q5_0": 6, "q5_1": 7, "q8_0": 8}
+GGML_BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34}
+
+
+def ggml_tensor_f16(path: str, name: str) -> np.ndarray:
+    """One tensor of a whisper.cpp ggml model file as f16, flat (wdr_ggml_tensor_f16; no GPU).
+    Quantized tensors go through the host definition of the block decode."""
+    lib = L.load()
+    out, n = C.POINTER(C.c_uint16)(), C.c_size_t()
+    L.check(lib.wdr_ggml_tensor_f16(path.encode(), name.encode(), C.byref(out), C.byref(n)))
+    try:
+        return np.ctypeslib.as_array(out, (max(1, n.value),))[:n.value].copy().view(np.float16)
+    finally:
+        lib.wdr_free(C.cast(out, C.c_void_p))
+
+
+def dbg_dequant(fmt, blocks, timing: bool = False):
+    """The load-time dequantization kernel (wdr_dbg_dequant): raw blocks (bytes / uint8 array) of
+    format `fmt` ('q4_0' .. 'q8_0' or the ggml type id) -> f16 [32 * n_blocks]; with timing also
+    the mean GPU milliseconds of 10 further launches."""
+    lib = L.load()
+    t = GGML_QUANT_TYPES.get(fmt, fmt)
+    raw = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if not isinstance(blocks, np.ndarray)
+                               else blocks.astype(np.uint8, copy=False).ravel())
+    bs = GGML_BLOCK_BYTES[t]
+    if raw.size % bs:
+        raise ValueError("%d bytes are not whole %d-byte blocks" % (raw.size, bs))
+    nb = raw.size // bs
+    out = np.empty(nb * 32, np.uint16)
+    ms = C.c_double()
+    L.check(lib.wdr_dbg_dequant(t, raw.ctypes.data_as(C.POINTER(C.c_uint8)), nb,
+                                out.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(ms) if timing else None))
+    return (out.view(np.float16), ms.value) if timing else out.view(np.float16)
 
 
 class WhisperContext:

@@ -153,6 +153,9 @@ _SIGS = {
     "wdr_dbg_set_early_fixup": (C.c_int, [vp, i32]),
     "wdr_dbg_set_gemm32": (C.c_int, [i32]),
     "wdr_ggml_info": (C.c_int, [cstr, P(i32), P(i64), P(i64)]),
+    "wdr_ggml_tensor_types": (C.c_int, [cstr, P(i64)]),
+    "wdr_ggml_tensor_f16": (C.c_int, [cstr, cstr, P(P(C.c_uint16)), P(sz)]),
+    "wdr_dbg_dequant": (C.c_int, [i32, P(C.c_uint8), sz, P(C.c_uint16), P(f64)]),
     "wdr_dbg_batch_step": (C.c_int, [vp, P(i32), sz, i32, i32, P(f64)]),
     "wdr_context_stage_times": (C.c_int, [vp, P(StageTimes)]),
     "wdr_context_hparams": (C.c_int, [vp, P(i32)]),
