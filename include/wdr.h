@@ -20,6 +20,10 @@
  *   wdr_context_create / _free           transcribe::create_context       src/transcribe.rs:89-166
  *   wdr_run_pipeline                     transcribe::run_transcription_pipeline src/transcribe.rs:323-535
  *   wdr_segment_list_free                (drop of Vec<Segment>)
+ * Not in the reference (additive, opt-in; the reference reads 16 kHz mono 16-bit WAV only):
+ *   wdr_audio_info                       header of any supported WAV (host only)
+ *   wdr_read_audio                       any supported WAV -> 16 kHz mono int16, converted on the GPU
+ *   wdr_engine_set_audio_convert         wdr_transcribe_audio reads its file through wdr_read_audio
  * The wdr_dbg_* functions are kernel-level test seams (parity tests call them).
  */
 #ifndef WDR_H
@@ -194,11 +198,28 @@ void wdr_engine_free(wdr_engine* e);
  * missing whisper model fails with "whisper file doesn't exist" as the reference does
  * (src/transcribe.rs:99-101), and a missing VAD / diarization model fails likewise. */
 int wdr_engine_set_synthetic(wdr_engine* e, const wdr_synthetic* syn);
+/* Audio conversion (an explicit opt-in).  1 = wdr_transcribe_audio reads its file through
+ * wdr_read_audio (on the engine's device): PCM 8 / 16 / 24 / 32-bit or IEEE f32, 1..8 channels,
+ * 1000..384000 Hz, downmixed and resampled to 16 kHz mono on the GPU.  0 (default) = the
+ * reference's read_wav and its errors.  Not in the Rust API. */
+int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on);
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* opts,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out);
 
 /* ---- seams ---- */
 int wdr_read_wav(const char* path, int16_t** samples, size_t* n);
+/* host only: info[5] = {fmt (0 u8, 1 i16, 2 i24, 3 i32, 4 f32), channels, rate, bits, block_align} of a
+ * RIFF/WAVE file with format tag 1 (PCM), 3 (IEEE float) or 0xFFFE (extensible, either of them);
+ * n_frames = whole frames of its data chunk.  A data size of 0xFFFFFFFF, or past the end of the
+ * file, means "to the end of the file" (piped writers); so does a size of 0, unless the rest of the
+ * file is empty or a run of whole chunks (LIST ...), in which case the data chunk is empty.  Bytes
+ * after an unsized data chunk are all taken as samples, trailing chunks included */
+int wdr_audio_info(const char* path, int32_t* info, uint64_t* n_frames);
+/* any supported WAV -> 16 kHz mono int16 (free with wdr_free): decode, downmix (mean of the
+ * channels) and a zero-phase polyphase Kaiser-sinc resampler, all on the GPU in bounded chunks;
+ * sample k of the result sits at k / 16000 s of the file.  A file that wdr_read_wav accepts comes
+ * back identical to wdr_read_wav's result, without touching the GPU */
+int wdr_read_audio(const char* path, int8_t has_gpu_device, int32_t gpu_device, int16_t** samples, size_t* n);
 /* test seam (host only, no GPU): parse a VAD / diarization model file the way the models load
  * it -- kind 0 whisper.cpp Silero ggml, 1 segmentation-3.0 ONNX, 2 CAM++ ONNX -- and return its
  * tensors under the oracle's names: names_out "name:count\n" per tensor (sorted), data_out the
@@ -372,6 +393,16 @@ int wdr_dbg_energy(const float* x, size_t n, float* out);
  * out_f16[32 * n_blocks] (f16 bits), bit-identical to wdr_ggml_tensor_f16's host definition; ms
  * (nullable): mean GPU time of 10 further back-to-back launches on the same buffers */
 int wdr_dbg_dequant(int32_t type, const uint8_t* blocks, size_t n_blocks, uint16_t* out_f16, double* ms);
+/* the audio conversion of n_frames raw interleaved frames held in memory (fmt / channels / rate as
+ * wdr_audio_info reports them) -> 16 kHz mono int16 (free with wdr_free).  host = 1: the host
+ * definition (no GPU); host = 0: the kernel path on the current device, bit-identical to it for
+ * every chunk_frames (0 = default); ms (nullable, host = 0): mean GPU time of 10 further
+ * back-to-back runs of the kernels on resident buffers */
+int wdr_dbg_audio_convert(const uint8_t* raw, uint64_t n_frames, int32_t fmt, int32_t channels, int32_t rate,
+                          uint64_t chunk_frames, int32_t host, int16_t** out, size_t* n_out, double* ms);
+/* host only: the resampler's coefficient table of a source rate: L = 16000 / g, M = rate / g
+ * (g = gcd), T taps per output and tab[L][T] (free with wdr_free); rate 16000: T = 0 */
+int wdr_dbg_resample_table(int32_t rate, int32_t* L, int32_t* M, int32_t* T, float** tab);
 /* one v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3) on raw per-lane operands: a / b [64 lanes][32 B],
  * scale registers sa / sb [64] (op_sel 0), out [64 lanes][4] accumulators */
 int wdr_dbg_mfma_scale(const uint8_t* a, const uint8_t* b, const int32_t* sa, const int32_t* sb, float* out);

@@ -30,6 +30,8 @@
 #include <vector>
 
 #include "../../include/wdr.h"
+#include "audio_file.h"
+#include "audio_gpu.h"
 #include "diarize.h"
 #include "formatting.h"
 #include "vad.h"
@@ -378,6 +380,8 @@ struct wdr_engine {
   std::string vad_loaded;   // model file the VAD was made from ("" = synthetic)
   std::unique_ptr<SegModel> seg;
   std::string seg_loaded;
+  bool audio_convert = false;   // wdr_engine_set_audio_convert: any supported WAV, converted on the GPU
+  std::unique_ptr<AudioConverter> conv;   // its streams, staging and per-rate tables (made on first use)
 };
 
 // src/vad.rs:6-85 on top of the GPU VAD: probabilities -> whisper.cpp segments (cs) -> the
@@ -1511,6 +1515,14 @@ int wdr_engine_set_synthetic(wdr_engine* e, const wdr_synthetic* syn) {
   })
 }
 
+int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on) {
+  WDR_GUARD({
+    WDR_USE(eng, e);
+    e->audio_convert = on != 0;
+    return 0;
+  })
+}
+
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* o,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out) {
   WDR_GUARD({
@@ -1528,7 +1540,9 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
     }
     if (o && o->translate_target && !(o->whisper_to_english == 1))
       return fail("translate_target: network translation is out of scope for libwdr");
-    std::vector<int16_t> pcm = read_wav_impl(audio_path);
+    std::vector<int16_t> pcm = e->audio_convert
+        ? read_audio_file(audio_path, e->cfg.has_gpu_device ? e->cfg.gpu_device : 0, &e->conv)
+        : read_wav_impl(audio_path);
     std::vector<wdr_speech_segment> segs;
     std::vector<int16_t> dpad;   // owns the samples of pyannote segments (they index the padded buffer)
     std::vector<std::pair<double, double>> vad_mask;   // VadMaskOracle input (VAD branch only)
@@ -1851,6 +1865,67 @@ int wdr_read_wav(const char* path, int16_t** samples, size_t* n) {
     *samples = (int16_t*)malloc(std::max<size_t>(1, v.size()) * 2);
     if (!v.empty()) memcpy(*samples, v.data(), v.size() * 2);
     *n = v.size();
+    return 0;
+  })
+}
+
+static int16_t* samples_out(const std::vector<int16_t>& v) {
+  int16_t* p = (int16_t*)malloc(std::max<size_t>(1, v.size()) * 2);
+  if (!p) throw std::bad_alloc();
+  if (!v.empty()) memcpy(p, v.data(), v.size() * 2);
+  return p;
+}
+
+int wdr_audio_info(const char* path, int32_t* info, uint64_t* n_frames) {
+  WDR_GUARD({
+    if (!path || !file_exists(path)) return fail("audio file doesn't exist");
+    const AudioInfo a = audio_parse(path);
+    info[0] = a.fmt; info[1] = a.channels; info[2] = a.rate; info[3] = a.bits; info[4] = a.block_align;
+    *n_frames = a.n_frames;
+    return 0;
+  })
+}
+
+int wdr_read_audio(const char* path, int8_t has_gpu_device, int32_t gpu_device, int16_t** samples, size_t* n) {
+  WDR_GUARD({
+    if (!path || !file_exists(path)) return fail("audio file doesn't exist");
+    const std::vector<int16_t> v = read_audio_file(path, has_gpu_device ? gpu_device : 0, nullptr);
+    *samples = samples_out(v);
+    *n = v.size();
+    return 0;
+  })
+}
+
+int wdr_dbg_audio_convert(const uint8_t* raw, uint64_t n_frames, int32_t fmt, int32_t channels, int32_t rate,
+                          uint64_t chunk_frames, int32_t host, int16_t** out, size_t* n_out, double* ms) {
+  WDR_GUARD({
+    std::vector<int16_t> v;
+    if (host) {
+      v = audio_convert_host(raw, n_frames, fmt, channels, rate);
+    } else {
+      if (fmt < 0 || fmt > 4) return fail("audio: sample format must be 0 (u8), 1 (i16), 2 (i24), 3 (i32) or 4 (f32)");
+      if (channels < 1 || channels > AUDIO_MAX_CHANNELS) return fail("unsupported channel count " + std::to_string(channels) + " (1 to 8)");
+      int dev = 0;
+      WDR_HIP(hipGetDevice(&dev));
+      AudioConverter conv(dev);
+      const size_t fb = (size_t)channels * audio_sample_bytes(fmt);
+      v = conv.convert([&](uint64_t frame, uint64_t n, uint8_t* dst) { memcpy(dst, raw + frame * fb, (size_t)n * fb); },
+                       n_frames, fmt, channels, rate, chunk_frames);
+      if (ms) *ms = conv.time_kernels(raw, n_frames, fmt, channels, rate, 10);
+    }
+    *out = samples_out(v);
+    *n_out = v.size();
+    return 0;
+  })
+}
+
+int wdr_dbg_resample_table(int32_t rate, int32_t* L, int32_t* M, int32_t* T, float** tab) {
+  WDR_GUARD({
+    const ResampleTable t = resample_table(rate);
+    *L = t.L; *M = t.M; *T = t.T;
+    *tab = (float*)malloc(std::max<size_t>(1, t.tab.size()) * 4);
+    if (!*tab) throw std::bad_alloc();
+    if (!t.tab.empty()) memcpy(*tab, t.tab.data(), t.tab.size() * 4);
     return 0;
   })
 }

@@ -37,6 +37,14 @@ void launch_synth_fill(void* dst, long long rows, int src_cols, int dst_cols, ui
 // -> 32 * n_blocks f16.  blocks and dst 16-byte aligned; the source is read up to its size rounded
 // up to a dword, so the caller pads its buffer that far
 void launch_dequant(int type, const void* blocks, long long n_blocks, f16* dst, hipStream_t s);
+// kernels/audio.hip: outputs k0 .. k0 + n_k of the conversion to 16 kHz mono int16 (audio_file.h)
+// into out[0 .. n_k).  raw (16-byte aligned) holds frames frame0 .. frame0 + n_stage of format fmt
+// with C channels and is read up to its size rounded up to 16 bytes, padding the caller provides;
+// frames outside it count as zero, so it must hold every frame of the file that these outputs'
+// taps reach.  tab [L][T] with T = 2 H, or null with L = M = H = 1, T = 0 for 16 kHz input
+void launch_audio_convert(const void* raw, int fmt, int C, float invC, long long frame0, long long n_stage,
+                          const float* tab, int L, int M, int H, int T, int16_t* out, long long k0, long long n_k,
+                          hipStream_t s);
 void launch_layernorm(const float* x, int ldx, const float* g, const float* b, f16* y, int ldy, int rows, int d,
                       hipStream_t s);
 void launch_embed(const f16* E, const float* P, const int* tok, const int* pos, int R, int d, float* x, hipStream_t s);

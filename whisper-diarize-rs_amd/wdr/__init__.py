@@ -301,6 +301,81 @@ def read_wav(path: str) -> np.ndarray:
     return out
 
 
+AUDIO_FORMATS = {"u8": 0, "i16": 1, "i24": 2, "i32": 3, "f32": 4}
+AUDIO_SAMPLE_BYTES = {0: 1, 1: 2, 2: 3, 3: 4, 4: 4}
+
+
+def _take_i16(lib, p, n):
+    try:
+        return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int16)
+    finally:
+        lib.wdr_free(C.cast(p, C.c_void_p))
+
+
+def audio_info(path: str) -> dict:
+    """Header of any supported WAV file (wdr_audio_info; host only): PCM 8 / 16 / 24 / 32-bit or
+    IEEE f32, 1..8 channels, 1000..384000 Hz, plain or extensible header.  Not in the reference."""
+    lib = L.load()
+    info = (C.c_int32 * 5)()
+    nf = C.c_uint64()
+    L.check(lib.wdr_audio_info(path.encode(), info, C.byref(nf)))
+    fmt, ch, rate, bits, align = list(info)
+    return {"fmt": fmt, "channels": ch, "rate": rate, "bits": bits, "block_align": align, "n_frames": nf.value}
+
+
+def read_audio(path: str, gpu_device: Optional[int] = None) -> np.ndarray:
+    """Any supported WAV -> 16 kHz mono int16, downmixed and resampled on the GPU (wdr_read_audio).
+    A file read_wav accepts comes back identical to read_wav's result without touching the GPU.
+    Not in the reference, which reads 16 kHz mono 16-bit files only."""
+    lib = L.load()
+    p = C.POINTER(C.c_int16)()
+    n = C.c_size_t()
+    L.check(lib.wdr_read_audio(path.encode(), 0 if gpu_device is None else 1, gpu_device or 0, C.byref(p), C.byref(n)))
+    return _take_i16(lib, p, n.value)
+
+
+def dbg_audio_convert(raw, fmt, channels: int, rate: int, chunk_frames: int = 0, host: bool = False,
+                      timing: bool = False):
+    """The audio conversion of raw interleaved frames (bytes / uint8 array) of format `fmt` ('u8',
+    'i16', 'i24', 'i32', 'f32' or 0..4) -> 16 kHz mono int16 (wdr_dbg_audio_convert).  host=True:
+    the host definition, no GPU; else the kernels, in chunks of chunk_frames input frames (0 = the
+    default); with timing also the mean GPU milliseconds of 10 further runs of the kernels."""
+    lib = L.load()
+    f = AUDIO_FORMATS.get(fmt, fmt)
+    if f not in AUDIO_SAMPLE_BYTES:
+        raise ValueError("unknown sample format %r" % (fmt,))
+    if not 1 <= channels <= 8:
+        raise ValueError("1 to 8 channels")
+    buf = np.ascontiguousarray(np.frombuffer(bytes(raw), np.uint8) if not isinstance(raw, np.ndarray)
+                               else raw.view(np.uint8).ravel())
+    fb = AUDIO_SAMPLE_BYTES[f] * channels
+    if buf.size % fb:
+        raise ValueError("%d bytes are not whole %d-byte frames" % (buf.size, fb))
+    p = C.POINTER(C.c_int16)()
+    n = C.c_size_t()
+    ms = C.c_double()
+    L.check(lib.wdr_dbg_audio_convert(buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size // fb, f, channels, rate,
+                                      chunk_frames, 1 if host else 0, C.byref(p), C.byref(n),
+                                      C.byref(ms) if timing and not host else None))
+    out = _take_i16(lib, p, n.value)
+    return (out, ms.value) if timing else out
+
+
+def dbg_resample_table(rate: int):
+    """(L, M, T, tab [L][T] float32): the resampler's coefficient table of a source rate
+    (wdr_dbg_resample_table; host only)."""
+    lib = L.load()
+    l, m, t = C.c_int32(), C.c_int32(), C.c_int32()
+    p = C.POINTER(C.c_float)()
+    L.check(lib.wdr_dbg_resample_table(rate, C.byref(l), C.byref(m), C.byref(t), C.byref(p)))
+    try:
+        n = l.value * t.value
+        tab = np.ctypeslib.as_array(p, shape=(max(1, n),))[:n].copy().reshape(l.value, t.value)
+    finally:
+        lib.wdr_free(C.cast(p, C.c_void_p))
+    return l.value, m.value, t.value, tab
+
+
 def vad_merge(segs_cs, samples: np.ndarray):
     """The crate's own post-processing of whisper.cpp VAD segments (src/vad.rs:33-84)."""
     lib = L.load()
@@ -807,7 +882,8 @@ class WhisperContext:
 class Engine:
     """Engine (src/engine.rs:52-217)."""
 
-    def __init__(self, cfg: Optional[EngineConfig] = None, synthetic: Optional[Synthetic] = None):
+    def __init__(self, cfg: Optional[EngineConfig] = None, synthetic: Optional[Synthetic] = None,
+                 audio_convert: bool = False):
         cfg = cfg or EngineConfig()
         lib = L.load()
         self._lib = lib
@@ -822,6 +898,13 @@ class Engine:
         if synthetic is not None:
             s = _syn(synthetic)
             L.check(lib.wdr_engine_set_synthetic(h, C.byref(s)))
+        if audio_convert:
+            self.set_audio_convert(True)
+
+    def set_audio_convert(self, on: bool):
+        """True: transcribe_audio takes any WAV read_audio takes, converted on the engine's GPU;
+        False (default): the reference's read_wav and its errors.  Not in the reference."""
+        L.check(self._lib.wdr_engine_set_audio_convert(self.h, 1 if on else 0))
 
     def transcribe_audio(self, audio_path: str, options: TranscribeOptions,
                          formatting_overrides=None, cb: Optional[Callbacks] = None) -> List[Segment]:

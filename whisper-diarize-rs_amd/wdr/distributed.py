@@ -3,7 +3,8 @@
 
 The reference transcribes a file on one device (src/engine.rs:65-200).  Here:
 
-1. Rank 0 holds the file's PCM (`read_wav`).  Its length is broadcast.
+1. Rank 0 holds the file's PCM (`read_wav`, or `read_audio` for a file of another rate, channel
+   count or sample format).  Its length is broadcast.
 2. Segmentation.  pyannote (src/engine.rs:89-122): its 10-s windows are independent, so the
    windows are split into G contiguous shards, each rank's PCM slice is scattered to it, every
    rank computes its windows' frame classes on its GPU, the classes are gathered to rank 0 and
