@@ -24,6 +24,9 @@
  *   wdr_audio_info                       header of any supported WAV (host only)
  *   wdr_read_audio                       any supported WAV -> 16 kHz mono int16, converted on the GPU
  *   wdr_engine_set_audio_convert         wdr_transcribe_audio reads its file through wdr_read_audio
+ *   wdr_read_audio_channels              any supported WAV -> 16 kHz int16 per channel (planar), on the GPU
+ *   wdr_engine_set_channel_split         wdr_transcribe_audio transcribes every channel on its own,
+ *                                        speaker = channel
  * The wdr_dbg_* functions are kernel-level test seams (parity tests call them).
  */
 #ifndef WDR_H
@@ -203,6 +206,21 @@ int wdr_engine_set_synthetic(wdr_engine* e, const wdr_synthetic* syn);
  * 1000..384000 Hz, downmixed and resampled to 16 kHz mono on the GPU.  0 (default) = the
  * reference's read_wav and its errors.  Not in the Rust API. */
 int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on);
+/* Channel split (an explicit opt-in, for recordings with one party per channel).  1 =
+ * wdr_transcribe_audio reads its file through wdr_read_audio_channels and transcribes every
+ * channel on its own, speaker = channel.  0 (default) = today's behaviour.  Independent of
+ * wdr_engine_set_audio_convert.  Not in the Rust API.
+ * Channel c = 0 .. C-1, in order, is treated as a mono file of that channel: segmented by VAD
+ * when enable_vad is 1 (else one segment), one pipeline run of its own (prompt chain, RNG reset,
+ * overlap clip, language detection), process_segments with its own VAD mask and its language's
+ * preset.  Every segment gets speaker_id = the decimal string of c + 1; the lists are merged by a
+ * stable sort on start (ties: lower channel first) and are not clipped against each other.
+ * detected_lang is that of the lowest channel that has one.  new_segment fires in channel order
+ * (not time order) with the channel's speaker_id; progress reports (c * 100 + pct) / C; a
+ * cancelled run ends the call as a cancelled single run ends, and no further channel starts.
+ * enable_diarize == 1 fails with "channel split labels speakers by channel: enable_diarize must
+ * not be set" before the file is read. */
+int wdr_engine_set_channel_split(wdr_engine* e, int8_t on);
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* opts,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out);
 
@@ -220,6 +238,11 @@ int wdr_audio_info(const char* path, int32_t* info, uint64_t* n_frames);
  * sample k of the result sits at k / 16000 s of the file.  A file that wdr_read_wav accepts comes
  * back identical to wdr_read_wav's result, without touching the GPU */
 int wdr_read_audio(const char* path, int8_t has_gpu_device, int32_t gpu_device, int16_t** samples, size_t* n);
+/* any supported WAV -> 16 kHz int16 per channel, planar: (*samples)[c * *n_per_channel + k];
+ * free with wdr_free.  Channel c equals wdr_read_audio of the mono file holding channel c.  A
+ * 16 kHz mono 16-bit file comes back as it is, without touching the GPU */
+int wdr_read_audio_channels(const char* path, int8_t has_gpu_device, int32_t gpu_device,
+                            int16_t** samples, size_t* n_per_channel, int32_t* channels);
 /* test seam (host only, no GPU): parse a VAD / diarization model file the way the models load
  * it -- kind 0 whisper.cpp Silero ggml, 1 segmentation-3.0 ONNX, 2 CAM++ ONNX -- and return its
  * tensors under the oracle's names: names_out "name:count\n" per tensor (sorted), data_out the
@@ -400,6 +423,11 @@ int wdr_dbg_dequant(int32_t type, const uint8_t* blocks, size_t n_blocks, uint16
  * back-to-back runs of the kernels on resident buffers */
 int wdr_dbg_audio_convert(const uint8_t* raw, uint64_t n_frames, int32_t fmt, int32_t channels, int32_t rate,
                           uint64_t chunk_frames, int32_t host, int16_t** out, size_t* n_out, double* ms);
+/* test seam, as wdr_dbg_audio_convert, of the channel-keeping conversion: planar
+ * (*out)[c * *n_per_channel + k].  host = 1 the definition (channel c = the mono definition on
+ * sample c of every frame), 0 the kernels (bit-identical for every chunk_frames); ms as there */
+int wdr_dbg_audio_split(const uint8_t* raw, uint64_t n_frames, int32_t fmt, int32_t channels, int32_t rate,
+                        uint64_t chunk_frames, int32_t host, int16_t** out, size_t* n_per_channel, double* ms);
 /* host only: the resampler's coefficient table of a source rate: L = 16000 / g, M = rate / g
  * (g = gcd), T taps per output and tab[L][T] (free with wdr_free); rate 16000: T = 0 */
 int wdr_dbg_resample_table(int32_t rate, int32_t* L, int32_t* M, int32_t* T, float** tab);

@@ -245,4 +245,23 @@ std::vector<int16_t> audio_convert_host(const uint8_t* raw, uint64_t n_frames, i
   return out;
 }
 
+// Channel c of the split is, by definition, audio_convert_host of the mono stream made of sample
+// c of every frame: nothing is computed here that the mono definition does not compute.
+std::vector<int16_t> audio_split_host(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate) {
+  if (fmt < 0 || fmt > 4) throw std::runtime_error("audio: sample format must be 0 (u8), 1 (i16), 2 (i24), 3 (i32) or 4 (f32)");
+  if (channels < 1 || channels > AUDIO_MAX_CHANNELS) throw std::runtime_error("unsupported channel count " + std::to_string(channels) + " (1 to 8)");
+  int L, M, H;
+  resample_dims(rate, &L, &M, &H);   // rejects a bad rate
+  const size_t sb = (size_t)audio_sample_bytes(fmt);
+  const uint64_t n_out = audio_n_out(n_frames, L, M);
+  std::vector<int16_t> out((size_t)channels * n_out);
+  std::vector<uint8_t> one((size_t)n_frames * sb);
+  for (int c = 0; c < channels; ++c) {
+    for (uint64_t j = 0; j < n_frames; ++j) memcpy(&one[j * sb], raw + (j * (uint64_t)channels + (uint64_t)c) * sb, sb);
+    const std::vector<int16_t> ch = audio_convert_host(one.data(), n_frames, fmt, 1, rate);
+    if (n_out) memcpy(&out[(size_t)c * n_out], ch.data(), (size_t)n_out * 2);
+  }
+  return out;
+}
+
 }  // namespace wdr

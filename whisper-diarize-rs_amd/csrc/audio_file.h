@@ -6,6 +6,8 @@
 //  audio_convert_host  the host definition of the conversion to 16 kHz mono int16: the meaning
 //                      of the feature, which the kernels (kernels/audio.hip) equal bit for bit.
 //                      Single-threaded; tests and documentation only, never a product fallback.
+//  audio_split_host    the same per channel, no downmix: the mono definition
+//                      applied to each channel's samples
 #pragma once
 
 #include <cstddef>
@@ -88,5 +90,8 @@ WDR_AUDIO_HD inline int16_t audio_quantize(float acc) {
 
 // raw: n_frames interleaved frames of `channels` samples of format fmt
 std::vector<int16_t> audio_convert_host(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate);
+// one channel per speaker: planar [channels][n_out] int16, channel c being
+// audio_convert_host of the mono stream made of sample c of every frame (no downmix, no invC)
+std::vector<int16_t> audio_split_host(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate);
 
 }  // namespace wdr

@@ -138,6 +138,18 @@ void AudioConverter::reserve(size_t in_bytes, size_t out_samples) {
 
 std::vector<int16_t> AudioConverter::convert(const Fill& fill, uint64_t n_frames, int fmt, int channels, int rate,
                                              uint64_t chunk_frames) {
+  return run(fill, n_frames, fmt, channels, rate, chunk_frames, false);
+}
+
+std::vector<int16_t> AudioConverter::convert_channels(const Fill& fill, uint64_t n_frames, int fmt, int channels,
+                                                      int rate, uint64_t chunk_frames) {
+  return run(fill, n_frames, fmt, channels, rate, chunk_frames, true);
+}
+
+// split: one output plane per channel (planar [channels][n_out]); else the one downmixed plane.
+// A slot's output staging holds a chunk's planes back to back, n outputs each
+std::vector<int16_t> AudioConverter::run(const Fill& fill, uint64_t n_frames, int fmt, int channels, int rate,
+                                         uint64_t chunk_frames, bool split) {
   WDR_CHECK(fmt >= 0 && fmt <= 4, "audio: sample format must be 0 (u8), 1 (i16), 2 (i24), 3 (i32) or 4 (f32)");
   WDR_CHECK(channels >= 1 && channels <= AUDIO_MAX_CHANNELS,
             "unsupported channel count " + std::to_string(channels) + " (1 to 8)");
@@ -148,15 +160,17 @@ std::vector<int16_t> AudioConverter::convert(const Fill& fill, uint64_t n_frames
   const uint64_t L = tb.L, M = tb.M, H = tb.H;
   const size_t fb = (size_t)channels * audio_sample_bytes(fmt);
   const float invC = 1.0f / (float)channels;
-  std::vector<int16_t> out(audio_n_out(n_frames, tb.L, tb.M));
+  const uint64_t planes = split ? (uint64_t)channels : 1, n_out = audio_n_out(n_frames, tb.L, tb.M);
+  std::vector<int16_t> out((size_t)(planes * n_out));
   if (out.empty()) return out;
   uint64_t cf = chunk_frames;
   if (cf == 0) {
+    // the output cap counts every plane, so a slot's output staging is the same for 8 channels as for 1
     cf = std::max<uint64_t>(1, kChunkBytes / fb);
-    cf = std::min(cf, std::max<uint64_t>(1, kChunkOutputs * M / L));
+    cf = std::min(cf, std::max<uint64_t>(1, kChunkOutputs / planes * M / L));
   }
   cf = std::min(cf, n_frames);
-  reserve((size_t)(cf + 2 * H) * fb, (size_t)(cf * L / M + 2));
+  reserve((size_t)(cf + 2 * H) * fb, (size_t)(planes * (cf * L / M + 2)));
 
   last.setup = now_s() - t_start;   // table, staging (pinned allocation the first time)
 
@@ -166,7 +180,8 @@ std::vector<int16_t> AudioConverter::convert(const Fill& fill, uint64_t n_frames
     const double t0 = now_s();
     WDR_HIP(hipEventSynchronize(ev_done_[slot]));
     last.wait += now_s() - t0;
-    memcpy(out.data() + pend[slot].k, h_out_[slot], pend[slot].n * 2);
+    for (uint64_t c = 0; c < planes; ++c)
+      memcpy(out.data() + c * n_out + pend[slot].k, h_out_[slot] + c * pend[slot].n, pend[slot].n * 2);
     pend[slot].on = false;
   };
   try {
@@ -184,10 +199,16 @@ std::vector<int16_t> AudioConverter::convert(const Fill& fill, uint64_t n_frames
       WDR_HIP(wdr_memcpy_async(d_in_[slot].p, h_in_[slot], up16(bytes), hipMemcpyHostToDevice, s_copy_));
       WDR_HIP(hipEventRecord(ev_copied_[slot], s_copy_));
       WDR_HIP(hipStreamWaitEvent(s_comp_, ev_copied_[slot], 0));
-      launch_audio_convert(d_in_[slot].p, fmt, channels, invC, (long long)s0, (long long)(s1 - s0),
-                           tb.tab.as<float>(), tb.L, tb.M, tb.H, tb.T, d_out_[slot].as<int16_t>(), (long long)k_lo,
+      if (split)
+        launch_audio_split(d_in_[slot].p, fmt, channels, (long long)s0, (long long)(s1 - s0), tb.tab.as<float>(), tb.L,
+                           tb.M, tb.H, tb.T, d_out_[slot].as<int16_t>(), (long long)(k_hi - k_lo), (long long)k_lo,
                            (long long)(k_hi - k_lo), s_comp_);
-      WDR_HIP(wdr_memcpy_async(h_out_[slot], d_out_[slot].p, (size_t)(k_hi - k_lo) * 2, hipMemcpyDeviceToHost, s_comp_));
+      else
+        launch_audio_convert(d_in_[slot].p, fmt, channels, invC, (long long)s0, (long long)(s1 - s0),
+                             tb.tab.as<float>(), tb.L, tb.M, tb.H, tb.T, d_out_[slot].as<int16_t>(), (long long)k_lo,
+                             (long long)(k_hi - k_lo), s_comp_);
+      WDR_HIP(wdr_memcpy_async(h_out_[slot], d_out_[slot].p, (size_t)(planes * (k_hi - k_lo)) * 2, hipMemcpyDeviceToHost,
+                               s_comp_));
       WDR_HIP(hipEventRecord(ev_done_[slot], s_comp_));
       pend[slot] = {true, k_lo, k_hi - k_lo};
       ++last.chunks;
@@ -209,7 +230,8 @@ std::vector<int16_t> AudioConverter::convert(const Fill& fill, uint64_t n_frames
   return out;
 }
 
-double AudioConverter::time_kernels(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate, int reps) {
+double AudioConverter::time_kernels(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate, int reps,
+                                    bool split) {
   WDR_CHECK(fmt >= 0 && fmt <= 4, "audio: sample format must be 0 (u8), 1 (i16), 2 (i24), 3 (i32) or 4 (f32)");
   WDR_CHECK(channels >= 1 && channels <= AUDIO_MAX_CHANNELS,
             "unsupported channel count " + std::to_string(channels) + " (1 to 8)");
@@ -218,12 +240,16 @@ double AudioConverter::time_kernels(const uint8_t* raw, uint64_t n_frames, int f
   const size_t bytes = (size_t)n_frames * channels * audio_sample_bytes(fmt);
   const uint64_t n_out = audio_n_out(n_frames, tb.L, tb.M);
   if (!n_out) return 0.0;
-  DevMem in(up16(bytes) + 16), out(n_out * 2);
+  DevMem in(up16(bytes) + 16), out((split ? (uint64_t)channels : 1) * n_out * 2);
   WDR_HIP(hipMemcpy(in.p, raw, bytes, hipMemcpyHostToDevice));
   const float invC = 1.0f / (float)channels;
   auto run = [&] {
-    launch_audio_convert(in.p, fmt, channels, invC, 0, (long long)n_frames, tb.tab.as<float>(), tb.L, tb.M, tb.H, tb.T,
-                         out.as<int16_t>(), 0, (long long)n_out, s_comp_);
+    if (split)
+      launch_audio_split(in.p, fmt, channels, 0, (long long)n_frames, tb.tab.as<float>(), tb.L, tb.M, tb.H, tb.T,
+                         out.as<int16_t>(), (long long)n_out, 0, (long long)n_out, s_comp_);
+    else
+      launch_audio_convert(in.p, fmt, channels, invC, 0, (long long)n_frames, tb.tab.as<float>(), tb.L, tb.M, tb.H, tb.T,
+                           out.as<int16_t>(), 0, (long long)n_out, s_comp_);
   };
   run();
   WDR_HIP(hipStreamSynchronize(s_comp_));
@@ -241,8 +267,10 @@ double AudioConverter::time_kernels(const uint8_t* raw, uint64_t n_frames, int f
   return (double)t / reps;
 }
 
-std::vector<int16_t> read_audio_file(const char* path, int device, std::unique_ptr<AudioConverter>* conv) {
+static std::vector<int16_t> read_audio_impl(const char* path, int device, std::unique_ptr<AudioConverter>* conv,
+                                            int* channels) {
   const AudioInfo a = audio_parse(path);
+  if (channels) *channels = a.channels;
   if (a.fmt == AUDIO_I16 && a.channels == 1 && a.rate == AUDIO_OUT_RATE) {
     std::vector<int16_t> out(a.n_frames);
     if (!out.empty()) audio_read_bytes(path, a.data_off, out.data(), out.size() * 2);
@@ -261,7 +289,20 @@ std::vector<int16_t> read_audio_file(const char* path, int device, std::unique_p
   std::unique_ptr<AudioConverter> own;
   if (!conv) conv = &own;
   if (!*conv) conv->reset(new AudioConverter(device));
-  return (*conv)->convert(fill, a.n_frames, a.fmt, a.channels, a.rate, 0);
+  return channels ? (*conv)->convert_channels(fill, a.n_frames, a.fmt, a.channels, a.rate, 0)
+                  : (*conv)->convert(fill, a.n_frames, a.fmt, a.channels, a.rate, 0);
+}
+
+std::vector<int16_t> read_audio_file(const char* path, int device, std::unique_ptr<AudioConverter>* conv) {
+  return read_audio_impl(path, device, conv, nullptr);
+}
+
+std::vector<int16_t> read_audio_file_channels(const char* path, int device, std::unique_ptr<AudioConverter>* conv,
+                                              int* channels) {
+  int c = 0;
+  std::vector<int16_t> out = read_audio_impl(path, device, conv, &c);
+  if (channels) *channels = c;
+  return out;
 }
 
 }  // namespace wdr

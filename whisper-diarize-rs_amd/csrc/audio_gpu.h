@@ -32,14 +32,23 @@ class AudioConverter {
   // does not depend on chunk_frames.  The caller's current device is restored on return.
   std::vector<int16_t> convert(const Fill& fill, uint64_t n_frames, int fmt, int channels, int rate,
                                uint64_t chunk_frames);
+  // one speaker per channel: planar [channels][n_out], channel c being the
+  // conversion of the mono stream made of sample c of every frame.  The same pipeline, halo rule
+  // and indexing as convert(); chunk_frames 0: about 32 MB of raw bytes, at most 16 Mi outputs
+  // counted over all channels together
+  std::vector<int16_t> convert_channels(const Fill& fill, uint64_t n_frames, int fmt, int channels, int rate,
+                                        uint64_t chunk_frames);
   // mean GPU milliseconds of `reps` back-to-back runs of the kernels over the whole input,
-  // resident on the device (one untimed run first)
-  double time_kernels(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate, int reps);
+  // resident on the device (one untimed run first); split: the channel-keeping kernels
+  double time_kernels(const uint8_t* raw, uint64_t n_frames, int fmt, int channels, int rate, int reps,
+                      bool split = false);
   Times last;
 
  private:
   struct DevTable { int L = 1, M = 1, H = 1, T = 0; DevMem tab; };
   const DevTable& table(int rate);
+  std::vector<int16_t> run(const Fill& fill, uint64_t n_frames, int fmt, int channels, int rate, uint64_t chunk_frames,
+                           bool split);
   void reserve(size_t in_bytes, size_t out_samples);
   void release_pinned();
 
@@ -56,5 +65,9 @@ class AudioConverter {
 // any supported WAV -> 16 kHz mono int16.  A 16 kHz mono 16-bit file is returned as it is, with
 // no GPU work; everything else goes through *conv (created on `device` when null)
 std::vector<int16_t> read_audio_file(const char* path, int device, std::unique_ptr<AudioConverter>* conv);
+// any supported WAV -> 16 kHz int16 per channel, planar [*channels][n] (n = size / *channels).  A
+// 16 kHz 16-bit file involves no filter, and a mono one is returned as it is with no GPU work
+std::vector<int16_t> read_audio_file_channels(const char* path, int device, std::unique_ptr<AudioConverter>* conv,
+                                              int* channels);
 
 }  // namespace wdr

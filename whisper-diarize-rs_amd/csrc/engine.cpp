@@ -382,6 +382,7 @@ struct wdr_engine {
   std::string seg_loaded;
   bool audio_convert = false;   // wdr_engine_set_audio_convert: any supported WAV, converted on the GPU
   std::unique_ptr<AudioConverter> conv;   // its streams, staging and per-rate tables (made on first use)
+  bool channel_split = false;   // wdr_engine_set_channel_split: every channel transcribed on its own, speaker = channel
 };
 
 // src/vad.rs:6-85 on top of the GPU VAD: probabilities -> whisper.cpp segments (cs) -> the
@@ -1075,7 +1076,8 @@ struct RngCarry {
 static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speech_segment>& segs,
                                      const wdr_transcribe_options* o, const wdr_diarize_options* dopts,
                                      const SynCfg& syn, const wdr_callbacks* cb, std::string* detected_lang,
-                                     bool* has_lang, bool raw = false, RngCarry* carry = nullptr) {
+                                     bool* has_lang, bool raw = false, RngCarry* carry = nullptr,
+                                     const char* fixed_speaker = nullptr) {
   const bool diarize = dopts != nullptr && !raw;
   const float dthr = dopts ? dopts->threshold : 0.5f;
   SpeakerManager speakers(dopts ? dopts->max_speakers : UINT64_MAX);
@@ -1239,6 +1241,9 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
         }
         s.has_speaker = true;
         s.speaker = speakers.assign(emb, 512, dthr);
+      } else if (fixed_speaker) {   // channel split: the caller knows who speaks
+        s.has_speaker = true;
+        s.speaker = fixed_speaker;
       }
       emit_segment(cb, s);
       if (cb && cb->progress) {
@@ -1523,6 +1528,14 @@ int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on) {
   })
 }
 
+int wdr_engine_set_channel_split(wdr_engine* e, int8_t on) {
+  WDR_GUARD({
+    WDR_USE(eng, e);
+    e->channel_split = on != 0;
+    return 0;
+  })
+}
+
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* o,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out) {
   WDR_GUARD({
@@ -1540,9 +1553,14 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
     }
     if (o && o->translate_target && !(o->whisper_to_english == 1))
       return fail("translate_target: network translation is out of scope for libwdr");
-    std::vector<int16_t> pcm = e->audio_convert
-        ? read_audio_file(audio_path, e->cfg.has_gpu_device ? e->cfg.gpu_device : 0, &e->conv)
-        : read_wav_impl(audio_path);
+    if (e->channel_split && o && o->enable_diarize == 1)
+      return fail("channel split labels speakers by channel: enable_diarize must not be set");
+    int n_ch = 1;   // channel split: pcm is planar [n_ch][pcm.size() / n_ch]
+    std::vector<int16_t> pcm =
+        e->channel_split
+            ? read_audio_file_channels(audio_path, e->cfg.has_gpu_device ? e->cfg.gpu_device : 0, &e->conv, &n_ch)
+        : e->audio_convert ? read_audio_file(audio_path, e->cfg.has_gpu_device ? e->cfg.gpu_device : 0, &e->conv)
+                           : read_wav_impl(audio_path);
     std::vector<wdr_speech_segment> segs;
     std::vector<int16_t> dpad;   // owns the samples of pyannote segments (they index the padded buffer)
     std::vector<std::pair<double, double>> vad_mask;   // VadMaskOracle input (VAD branch only)
@@ -1560,6 +1578,87 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
       if (f.empty() && !e->syn_set) throw std::runtime_error(std::string(what) + " file doesn't exist");
       return f;
     };
+    if (e->channel_split) {
+      // each channel is what a mono file of it would be -- its own segmentation, its
+      // own run_pipeline call (prompt chain, RNG, overlap clip, language detection), its own mask
+      // and preset -- labelled with its channel number; the lists are merged by start time and
+      // not clipped against each other, since two channels may speak at once
+      struct Scaled {   // progress of channel c of C: (c * 100 + pct) / C
+        const wdr_callbacks* cb;
+        int c, C;
+        static void progress(void* u, int32_t pct, int32_t type, const char* label) {
+          const Scaled* s = (const Scaled*)u;
+          s->cb->progress(s->cb->user, (int32_t)((s->c * 100 + pct) / s->C), type, label);
+        }
+        static void new_segment(void* u, const wdr_segment* seg) {
+          const Scaled* s = (const Scaled*)u;
+          s->cb->new_segment(s->cb->user, seg);
+        }
+        static int is_cancelled(void* u) {
+          const Scaled* s = (const Scaled*)u;
+          return s->cb->is_cancelled(s->cb->user);
+        }
+      };
+      const size_t n = pcm.size() / (size_t)n_ch;
+      std::vector<Seg> all;
+      std::string lang;
+      bool has_lang = false;
+      for (int c = 0; c < n_ch; ++c) {
+        const int16_t* x = pcm.data() + (size_t)c * n;
+        segs.clear();
+        vad_mask.clear();
+        if (vad) {
+          const std::string vp = resolve(e->vad_path, "models--ggml-org--whisper-vad", "ggml-silero-v5.1.2.bin", "VAD model");
+          if (!e->vad || e->vad_loaded != vp) {
+            e->vad.reset();
+            e->vad = std::make_unique<VadModel>(dev, vp);
+            e->vad_loaded = vp;
+          }
+          vad_get_segments(*e->vad, x, n, &vad_mask, &segs);
+        } else {
+          segs.push_back({0.0, (double)n / 16000.0, x, n});
+        }
+        Scaled sc{cb, c, n_ch};
+        wdr_callbacks wcb{};
+        if (cb) {
+          wcb.user = &sc;
+          wcb.progress = cb->progress ? &Scaled::progress : nullptr;
+          wcb.new_segment = cb->new_segment ? &Scaled::new_segment : nullptr;
+          wcb.is_cancelled = cb->is_cancelled ? &Scaled::is_cancelled : nullptr;
+        }
+        if (segs.empty()) {   // VAD found no speech on this channel: it contributes nothing
+          if (cb && cb->progress) Scaled::progress(&sc, 100, 1, "Transcribing audio");
+          continue;
+        }
+        if (it == e->contexts.end())
+          it = e->contexts.emplace(model, make_context(model, e->cfg.has_gpu_device, e->cfg.gpu_device, e->cfg.use_gpu,
+                                                       e->cfg.enable_dtw, e->syn, model_path))
+                   .first;
+        const std::string label = std::to_string(c + 1);
+        std::string clang;
+        bool chas = false;
+        // a cancelled run throws, as in the default mode: no further channel is started
+        std::vector<Seg> res = run_pipeline(it->second.get(), segs, o, nullptr, e->syn, cb ? &wcb : nullptr, &clang,
+                                            &chas, false, nullptr, label.c_str());
+        const std::string eff = chas ? clang : ((o && o->lang) ? std::string(o->lang) : std::string("auto"));
+        PostProcessConfig pcfg = config_for_language(eff);
+        apply_overrides(pcfg, fmt);
+        res = from_fmt(process_segments(to_fmt(res), pcfg, vad ? &vad_mask : nullptr));
+        for (Seg& s : res) {
+          s.has_speaker = true;
+          s.speaker = label;
+          all.push_back(std::move(s));
+        }
+        if (chas && !has_lang) {
+          lang = clang;
+          has_lang = true;
+        }
+      }
+      // channel order within equal starts: the lists were appended in channel order
+      std::stable_sort(all.begin(), all.end(), [](const Seg& a, const Seg& b) { return a.start < b.start; });
+      *out = to_list(all, has_lang ? &lang : nullptr);
+      return 0;
+    }
     bool diarize = false;
     std::string seg_path, emb_path;
     if (o && o->enable_diarize == 1) {
@@ -1892,6 +1991,46 @@ int wdr_read_audio(const char* path, int8_t has_gpu_device, int32_t gpu_device, 
     const std::vector<int16_t> v = read_audio_file(path, has_gpu_device ? gpu_device : 0, nullptr);
     *samples = samples_out(v);
     *n = v.size();
+    return 0;
+  })
+}
+
+int wdr_read_audio_channels(const char* path, int8_t has_gpu_device, int32_t gpu_device, int16_t** samples,
+                            size_t* n_per_channel, int32_t* channels) {
+  WDR_GUARD({
+    if (!samples || !n_per_channel || !channels) return fail("null pointer");
+    if (!path || !file_exists(path)) return fail("audio file doesn't exist");
+    int c = 0;
+    const std::vector<int16_t> v = read_audio_file_channels(path, has_gpu_device ? gpu_device : 0, nullptr, &c);
+    *samples = samples_out(v);
+    *n_per_channel = v.size() / (size_t)c;
+    *channels = c;
+    return 0;
+  })
+}
+
+int wdr_dbg_audio_split(const uint8_t* raw, uint64_t n_frames, int32_t fmt, int32_t channels, int32_t rate,
+                        uint64_t chunk_frames, int32_t host, int16_t** out, size_t* n_per_channel, double* ms) {
+  WDR_GUARD({
+    if (!out || !n_per_channel || (!raw && n_frames)) return fail("null pointer");
+    if (fmt < 0 || fmt > 4) return fail("audio: sample format must be 0 (u8), 1 (i16), 2 (i24), 3 (i32) or 4 (f32)");
+    if (channels < 1 || channels > AUDIO_MAX_CHANNELS) return fail("unsupported channel count " + std::to_string(channels) + " (1 to 8)");
+    int L, M, H;
+    resample_dims(rate, &L, &M, &H);   // rejects a bad rate
+    std::vector<int16_t> v;
+    if (host) {
+      v = audio_split_host(raw, n_frames, fmt, channels, rate);
+    } else {
+      int dev = 0;
+      WDR_HIP(hipGetDevice(&dev));
+      AudioConverter conv(dev);
+      const size_t fb = (size_t)channels * audio_sample_bytes(fmt);
+      v = conv.convert_channels([&](uint64_t frame, uint64_t n, uint8_t* dst) { memcpy(dst, raw + frame * fb, (size_t)n * fb); },
+                                n_frames, fmt, channels, rate, chunk_frames);
+      if (ms) *ms = conv.time_kernels(raw, n_frames, fmt, channels, rate, 10, true);
+    }
+    *out = samples_out(v);
+    *n_per_channel = v.size() / (size_t)channels;
     return 0;
   })
 }

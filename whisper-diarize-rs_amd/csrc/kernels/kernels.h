@@ -45,6 +45,11 @@ void launch_dequant(int type, const void* blocks, long long n_blocks, f16* dst, 
 void launch_audio_convert(const void* raw, int fmt, int C, float invC, long long frame0, long long n_stage,
                           const float* tab, int L, int M, int H, int T, int16_t* out, long long k0, long long n_k,
                           hipStream_t s);
+// the channel-keeping form: the same outputs of each of the C channels on its own (no downmix),
+// channel c into out[c * out_stride .. c * out_stride + n_k); out_stride >= n_k
+void launch_audio_split(const void* raw, int fmt, int C, long long frame0, long long n_stage, const float* tab, int L,
+                        int M, int H, int T, int16_t* out, long long out_stride, long long k0, long long n_k,
+                        hipStream_t s);
 void launch_layernorm(const float* x, int ldx, const float* g, const float* b, f16* y, int ldy, int rows, int d,
                       hipStream_t s);
 void launch_embed(const f16* E, const float* P, const int* tok, const int* pos, int R, int d, float* x, hipStream_t s);

@@ -361,6 +361,46 @@ def dbg_audio_convert(raw, fmt, channels: int, rate: int, chunk_frames: int = 0,
     return (out, ms.value) if timing else out
 
 
+def read_audio_channels(path: str, gpu_device: Optional[int] = None) -> np.ndarray:
+    """Any supported WAV -> 16 kHz int16 [channels][n], every channel resampled on its own on the
+    GPU (wdr_read_audio_channels): channel c equals read_audio of the mono file holding channel c.
+    A 16 kHz mono 16-bit file comes back as read_wav's result without touching the GPU.  Not in the
+    reference."""
+    lib = L.load()
+    p = C.POINTER(C.c_int16)()
+    n = C.c_size_t()
+    ch = C.c_int32()
+    L.check(lib.wdr_read_audio_channels(path.encode(), 0 if gpu_device is None else 1, gpu_device or 0, C.byref(p),
+                                        C.byref(n), C.byref(ch)))
+    return _take_i16(lib, p, n.value * ch.value).reshape(ch.value, n.value)
+
+
+def dbg_audio_split(raw, fmt, channels: int, rate: int, chunk_frames: int = 0, host: bool = False,
+                    timing: bool = False):
+    """dbg_audio_convert's channel-keeping form (wdr_dbg_audio_split): raw interleaved frames ->
+    16 kHz int16 [channels][n_out], no downmix.  host=True: the definition (channel c is the mono
+    definition on sample c of every frame), no GPU; else the kernels; timing as there."""
+    lib = L.load()
+    f = AUDIO_FORMATS.get(fmt, fmt)
+    if f not in AUDIO_SAMPLE_BYTES:
+        raise ValueError("unknown sample format %r" % (fmt,))
+    if not 1 <= channels <= 8:
+        raise ValueError("1 to 8 channels")
+    buf = np.ascontiguousarray(np.frombuffer(bytes(raw), np.uint8) if not isinstance(raw, np.ndarray)
+                               else raw.view(np.uint8).ravel())
+    fb = AUDIO_SAMPLE_BYTES[f] * channels
+    if buf.size % fb:
+        raise ValueError("%d bytes are not whole %d-byte frames" % (buf.size, fb))
+    p = C.POINTER(C.c_int16)()
+    n = C.c_size_t()
+    ms = C.c_double()
+    L.check(lib.wdr_dbg_audio_split(buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size // fb, f, channels, rate,
+                                    chunk_frames, 1 if host else 0, C.byref(p), C.byref(n),
+                                    C.byref(ms) if timing and not host else None))
+    out = _take_i16(lib, p, n.value * channels).reshape(channels, n.value)
+    return (out, ms.value) if timing else out
+
+
 def dbg_resample_table(rate: int):
     """(L, M, T, tab [L][T] float32): the resampler's coefficient table of a source rate
     (wdr_dbg_resample_table; host only)."""
@@ -883,7 +923,7 @@ class Engine:
     """Engine (src/engine.rs:52-217)."""
 
     def __init__(self, cfg: Optional[EngineConfig] = None, synthetic: Optional[Synthetic] = None,
-                 audio_convert: bool = False):
+                 audio_convert: bool = False, channel_split: bool = False):
         cfg = cfg or EngineConfig()
         lib = L.load()
         self._lib = lib
@@ -900,11 +940,19 @@ class Engine:
             L.check(lib.wdr_engine_set_synthetic(h, C.byref(s)))
         if audio_convert:
             self.set_audio_convert(True)
+        if channel_split:
+            self.set_channel_split(True)
 
     def set_audio_convert(self, on: bool):
         """True: transcribe_audio takes any WAV read_audio takes, converted on the engine's GPU;
         False (default): the reference's read_wav and its errors.  Not in the reference."""
         L.check(self._lib.wdr_engine_set_audio_convert(self.h, 1 if on else 0))
+
+    def set_channel_split(self, on: bool):
+        """True: transcribe_audio takes any WAV read_audio_channels takes and transcribes every
+        channel on its own; segments carry speaker_id "1", "2", ... = channel, merged by start time.
+        enable_diarize must not be set.  False (default): as before.  Not in the reference."""
+        L.check(self._lib.wdr_engine_set_channel_split(self.h, 1 if on else 0))
 
     def transcribe_audio(self, audio_path: str, options: TranscribeOptions,
                          formatting_overrides=None, cb: Optional[Callbacks] = None) -> List[Segment]:

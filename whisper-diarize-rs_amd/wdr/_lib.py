@@ -119,6 +119,9 @@ _SIGS = {
     "wdr_read_audio": (C.c_int, [cstr, i8, i32, P(P(C.c_int16)), P(sz)]),
     "wdr_engine_set_audio_convert": (C.c_int, [vp, i8]),
     "wdr_dbg_audio_convert": (C.c_int, [P(C.c_uint8), u64, i32, i32, i32, u64, i32, P(P(C.c_int16)), P(sz), P(f64)]),
+    "wdr_read_audio_channels": (C.c_int, [cstr, i8, i32, P(P(C.c_int16)), P(sz), P(i32)]),
+    "wdr_dbg_audio_split": (C.c_int, [P(C.c_uint8), u64, i32, i32, i32, u64, i32, P(P(C.c_int16)), P(sz), P(f64)]),
+    "wdr_engine_set_channel_split": (C.c_int, [vp, i8]),
     "wdr_dbg_resample_table": (C.c_int, [i32, P(i32), P(i32), P(i32), P(P(f32))]),
     "wdr_dbg_model_file": (C.c_int, [i32, cstr, P(C.c_void_p), P(P(f32)), P(sz)]),
     "wdr_process_segments": (C.c_int, [P(Segment), sz, cstr, P(FormattingOverrides), i8, P(f64), sz,
