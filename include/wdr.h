@@ -489,6 +489,38 @@ int wdr_dbg_attn(const uint16_t* q, const uint16_t* k, const uint16_t* v, int32_
 int wdr_dbg_xattn(const uint16_t* q, const uint16_t* kv, const int32_t* row_slot, const int32_t* grp, int32_t R,
                   int32_t S, int32_t H, int32_t iters, float* out);
 
+/* ---- decode-step seams.  Every one checks its arguments on the host and returns an error for an
+ * out-of-range value instead of launching: row_seq in [0, n_seq), row_pos in [0, min(T, 448)) (the
+ * self-attention kernel holds at most 448 scores), d = 64 H, K in [1, 8], R in [1, 8] logit rows ---- */
+/* decode-step self-attention (k_dec_self_attn, one launch, scale 1/8): row r of q [R][64 H] (f16 bits)
+ * attends over keys 0 .. row_pos[r] of sequence row_seq[r] of the caches kc / vc [n_seq][T][64 H]
+ * (f16 bits); out [R][64 H] (f16 -> f32) */
+int wdr_dbg_self_attn(const uint16_t* q, const uint16_t* kc, const uint16_t* vc, int32_t n_seq, int32_t T,
+                      const int32_t* row_seq, const int32_t* row_pos, int32_t R, int32_t H, float* out);
+/* the decoder's fused Q/K/V projection (row kernel, cache-scatter epilogue): a [M][K], w [3 d][K] (f16
+ * bits), bias [3 d] (nullable); row r's Q -> q_out [M][d] (f16 -> f32), its K / V -> row (row_seq[r],
+ * row_pos[r]) of kc_io / vc_io [n_seq][T][d] (f16 bits; uploaded, updated, copied back).  K % 32 == 0;
+ * the rows must name distinct cache rows */
+int wdr_dbg_proj_qkv(const uint16_t* a_f16, const uint16_t* w_f16, const float* bias, int32_t M, int32_t d, int32_t K,
+                     const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
+                     uint16_t* vc_io, float* q_out);
+/* wdr_dbg_logits' inputs, then the beam-search top-K of the same rows (k_logits_topk +
+ * k_logits_topk_final): ids [R][K], f [R][K][2] = {p, log p}, best first, ties by lower id; a row
+ * with fewer than K finite candidates ends with {id -1, p 0, log p -inf} */
+int wdr_dbg_logits_topk(wdr_context* c, const float* logits, int32_t R, const int32_t* ctl, const float* temperature,
+                        float max_initial_ts, int32_t suppress_blank, int32_t K, int32_t* ids_out, float* f_out);
+/* wdr_dbg_logits' inputs, then the sampling distribution of the same rows (k_logits_probs):
+ * probs / logprobs [R][n_vocab], 0 / -inf on masked tokens */
+int wdr_dbg_logits_probs(wdr_context* c, const float* logits, int32_t R, const int32_t* ctl, const float* temperature,
+                         float max_initial_ts, int32_t suppress_blank, float* probs_out, float* logprobs_out);
+/* the first n_rows self-attention cache rows of decoder sequence seq (0 .. 7, chain 0) in every text
+ * layer, k / v [n_text_layer][n_rows][d] f16 bits: write != 0 stores them, 0 reads them back */
+int wdr_dbg_kv_rows(wdr_context* c, int32_t seq, int32_t n_rows, int32_t write, uint16_t* k, uint16_t* v);
+/* the beam reorder (two k_kv_copy phases through scratch sequences): sequence dst[i] takes the first
+ * n_rows cached rows that sequence src[i] held before the call, i < n <= 8; a destination named twice
+ * is an error */
+int wdr_dbg_kv_reorder(wdr_context* c, const int32_t* src, const int32_t* dst, int32_t n, int32_t n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2781,4 +2781,146 @@ int wdr_dbg_xattn(const uint16_t* q, const uint16_t* kv, const int32_t* row_slot
   })
 }
 
+// (row_seq, row_pos) of the decode-step seams: checked on the host, never launched out of range
+// (k_dec_self_attn holds at most 448 scores in LDS; the cache has n_seq x T rows)
+static void check_rows(const int32_t* row_seq, const int32_t* row_pos, int R, int n_seq, int T, const char* what) {
+  for (int r = 0; r < R; ++r) {
+    WDR_CHECK(row_seq[r] >= 0 && row_seq[r] < n_seq, std::string(what) + ": row_seq out of range");
+    WDR_CHECK(row_pos[r] >= 0 && row_pos[r] < std::min(T, 448), std::string(what) + ": row_pos out of range");
+  }
+}
+
+// decode-step self-attention (kernels/attn.hip k_dec_self_attn) as rows_forward launches it: row
+// r attends over keys 0 .. row_pos[r] of cache sequence row_seq[r]
+int wdr_dbg_self_attn(const uint16_t* q, const uint16_t* kc, const uint16_t* vc, int32_t n_seq, int32_t T,
+                      const int32_t* row_seq, const int32_t* row_pos, int32_t R, int32_t H, float* out) {
+  WDR_GUARD({
+    WDR_CHECK(q && kc && vc && row_seq && row_pos && out, "dbg self-attn: null argument");
+    WDR_CHECK(R >= 1 && R <= 4096 && H >= 1 && H <= 32 && n_seq >= 1 && n_seq <= 64 && T >= 1 && T <= 4096,
+              "dbg self-attn: bad shape");
+    check_rows(row_seq, row_pos, R, n_seq, T, "dbg self-attn");
+    const int d = H * 64;
+    const size_t cache = (size_t)n_seq * T * d * 2;
+    DevMem dq((size_t)R * d * 2), dk(cache), dv(cache), dout((size_t)R * d * 2), ds(R * 4), dp(R * 4);
+    WDR_HIP(hipMemcpy(dq.p, q, dq.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dk.p, kc, cache, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dv.p, vc, cache, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(ds.p, row_seq, R * 4, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dp.p, row_pos, R * 4, hipMemcpyHostToDevice));
+    DecSelfArgs sa{dq.as<f16>(), d, dk.as<f16>(), dv.as<f16>(), (long long)T * d, d, ds.as<int>(), dp.as<int>(),
+                   dout.as<f16>(), d, 0.125f};
+    launch_dec_self_attn(sa, R, H, nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    std::vector<f16> h((size_t)R * d);
+    WDR_HIP(hipMemcpy(h.data(), dout.p, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) out[i] = (float)h[i];
+    return 0;
+  })
+}
+
+// the decoder's fused QKV projection (row kernel, EPI_QKV_CACHE): Q of every row to q_out, its
+// K / V into cache row (row_seq, row_pos) of the caller's cache arrays (uploaded, updated, copied
+// back).  Rows must name distinct cache rows (two rows writing one would race)
+int wdr_dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t d, int32_t K,
+                     const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
+                     uint16_t* vc_io, float* q_out) {
+  WDR_GUARD({
+    WDR_CHECK(a16 && w16 && row_seq && row_pos && kc_io && vc_io && q_out, "dbg qkv projection: null argument");
+    WDR_CHECK(M >= 1 && M <= 4096 && d >= 64 && d <= 2048 && d % 64 == 0 && d % 8 == 0 && K >= 32 && K <= 8192 &&
+                  K % 32 == 0 && n_seq >= 1 && n_seq <= 64 && T >= 1 && T <= 4096,
+              "dbg qkv projection: bad shape (d = 64 H, K % 32)");
+    check_rows(row_seq, row_pos, M, n_seq, T, "dbg qkv projection");
+    std::set<long long> seen;
+    for (int r = 0; r < M; ++r)
+      WDR_CHECK(seen.insert((long long)row_seq[r] * T + row_pos[r]).second, "dbg qkv projection: a cache row named twice");
+    const int N = 3 * d;
+    const size_t cache = (size_t)n_seq * T * d * 2;
+    DevMem da((size_t)M * K * 2), dw((size_t)N * K * 2), db(bias ? (size_t)N * 4 : 0), dq((size_t)M * d * 2), dk(cache),
+        dv(cache), ds(M * 4), dp(M * 4);
+    WDR_HIP(hipMemcpy(da.p, a16, da.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dw.p, w16, dw.bytes, hipMemcpyHostToDevice));
+    if (bias) WDR_HIP(hipMemcpy(db.p, bias, db.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dk.p, kc_io, cache, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dv.p, vc_io, cache, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(ds.p, row_seq, M * 4, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dp.p, row_pos, M * 4, hipMemcpyHostToDevice));
+    ProjArgs a{da.as<f16>(), K, dw.as<f16>(), K, bias ? db.as<float>() : nullptr, dq.p, d, nullptr, 0, M, N, K,
+               EPI_QKV_CACHE};
+    a.rows_mma = 1;
+    a.kc = dk.as<f16>();
+    a.vc = dv.as<f16>();
+    a.seq_stride = (long long)T * d;
+    a.row_seq = ds.as<int>();
+    a.row_pos = dp.as<int>();
+    a.d = d;
+    launch_proj(a, nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    std::vector<f16> h((size_t)M * d);
+    WDR_HIP(hipMemcpy(h.data(), dq.p, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) q_out[i] = (float)h[i];
+    WDR_HIP(hipMemcpy(kc_io, dk.p, cache, hipMemcpyDeviceToHost));
+    WDR_HIP(hipMemcpy(vc_io, dv.p, cache, hipMemcpyDeviceToHost));
+    return 0;
+  })
+}
+
+static void dbg_ctls(const int32_t* ctl, const float* temperature, int R, std::vector<LogitsCtl>& lc) {
+  lc.resize(R);
+  for (int r = 0; r < R; ++r) {
+    const int32_t* q = ctl + 7 * r;
+    lc[r] = LogitsCtl{q[0], q[1], q[2], q[3], q[4], q[5], q[6], temperature[r]};
+  }
+}
+
+int wdr_dbg_logits_topk(wdr_context* c, const float* logits, int32_t R, const int32_t* ctl, const float* temperature,
+                        float max_initial_ts, int32_t suppress_blank, int32_t K, int32_t* ids_out, float* f_out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(logits && ctl && temperature && ids_out && f_out, "dbg_logits_topk: null argument");
+    WDR_CHECK(R >= 1 && R <= 8, "dbg_logits_topk: 1..8 rows");
+    WDR_CHECK(K >= 1 && K <= BEAM_KMAX, "dbg_logits_topk: K out of range");
+    std::vector<LogitsCtl> lc;
+    dbg_ctls(ctl, temperature, R, lc);
+    std::vector<BeamCand> bc((size_t)R * K);
+    c->st->dbg_logits_topk(logits, R, lc.data(), max_initial_ts, suppress_blank != 0, K, bc.data());
+    for (int i = 0; i < R * K; ++i) {
+      ids_out[i] = bc[i].id;
+      f_out[2 * i] = bc[i].p;
+      f_out[2 * i + 1] = bc[i].plog;
+    }
+    return 0;
+  })
+}
+
+int wdr_dbg_logits_probs(wdr_context* c, const float* logits, int32_t R, const int32_t* ctl, const float* temperature,
+                         float max_initial_ts, int32_t suppress_blank, float* probs_out, float* logprobs_out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(logits && ctl && temperature && probs_out && logprobs_out, "dbg_logits_probs: null argument");
+    WDR_CHECK(R >= 1 && R <= 8, "dbg_logits_probs: 1..8 rows");
+    std::vector<LogitsCtl> lc;
+    dbg_ctls(ctl, temperature, R, lc);
+    c->st->dbg_logits_probs(logits, R, lc.data(), max_initial_ts, suppress_blank != 0, probs_out, logprobs_out);
+    return 0;
+  })
+}
+
+int wdr_dbg_kv_rows(wdr_context* c, int32_t seq, int32_t n_rows, int32_t write, uint16_t* k, uint16_t* v) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(k && v, "dbg_kv_rows: null argument");
+    c->st->dbg_kv_rows(seq, n_rows, write != 0, k, v);
+    return 0;
+  })
+}
+
+int wdr_dbg_kv_reorder(wdr_context* c, const int32_t* src, const int32_t* dst, int32_t n, int32_t n_rows) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(src && dst, "dbg_kv_reorder: null argument");
+    c->st->dbg_kv_reorder(src, dst, n, n_rows);
+    return 0;
+  })
+}
+
 }  // extern "C"

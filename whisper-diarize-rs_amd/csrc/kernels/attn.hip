@@ -13,7 +13,7 @@
 //  * k_xattn_partial / k_xattn_combine — split-K ("flash decode") cross-attention for the
 //    <=8 decoder rows of a step: the 1500 cross keys are split in 128-key chunks over
 //    workgroups so every CU streams the cross K/V once for all beams.
-//  * k_aheads_capture — softmax(QK^T) of the alignment heads over all 1500 keys.
+//  * k_aheads_capture_rows — softmax(QK^T) of the alignment heads over all 1500 keys.
 #include <cstdlib>
 
 #include "../common.h"
@@ -661,37 +661,9 @@ void launch_xattn(const XAttnArgs& a, hipStream_t s) {
 
 // ---------------------------------------------------------------- alignment-head capture
 
-__global__ __launch_bounds__(256) void k_aheads_capture(CaptureArgs a) {
-  __shared__ float qs[64];
-  const int r = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
-  const int h = a.heads[i];
-  if (tid < 64) qs[tid] = (float)a.q[(long long)r * a.ldq + h * 64 + tid];
-  __syncthreads();
-  // identical arithmetic to k_flash_attn's f32 accumulate is not guaranteed; the capture
-  // recomputes q.k in f32 from the same f16 operands.
-  const float2 ml = a.ml[(long long)h * a.R + r];
-  const float inv = 1.f / ml.y;
-  float* out = a.out + ((long long)(a.slot0 + i) * a.R + r) * a.Tk;
-  for (int key = tid; key < a.Tk; key += 256) {
-    const f16* kr = a.k + (long long)key * a.ldk + h * a.hs;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 64; c += 8) {
-      const f16x8 kv = *(const f16x8*)(kr + c);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += qs[c + e] * (float)kv[e];
-    }
-    out[key] = __expf(s * a.scale - ml.x) * inv;
-  }
-}
-
-void launch_aheads_capture(const CaptureArgs& a, int n_sel, hipStream_t s) {
-  WDR_KLAUNCH(k_aheads_capture, dim3(a.R, n_sel), dim3(256), 0, s, a);
-  WDR_HIP(hipGetLastError());
-}
-
-// k_aheads_capture for rows of several DTW re-forwards in one batch (rows_forward): each
-// capture row reads its own slot and writes its own request's buffer
+// softmax(QK^T) of the alignment heads for rows of several DTW re-forwards in one batch
+// (rows_forward): q.k recomputed in f32 from the same f16 operands, normalised with the
+// combine's (max, sum); each capture row reads its own slot and writes its own request's buffer
 __global__ __launch_bounds__(256) void k_aheads_capture_rows(CaptureRowsArgs a) {
   __shared__ float qs[64];
   const int j = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;

@@ -8,7 +8,6 @@
 //  k_energy          a3  whisper.cpp get_signal_energy, bit-exact (same f32 add order).
 //  k_layernorm       a6/a9 ggml_norm (double sums) * gamma + beta -> f16 matmul input.
 //  k_embed           a9  token + positional embedding.
-//  k_kv_scatter      a9  K/V rows of the current tokens into the self-attention cache.
 //  k_logits_process  a10 whisper.cpp whisper_process_logits + greedy pick + timestamp
 //                        probabilities + no-speech probability, one workgroup per row.
 //  k_dtw_norm / k_dtw_medmean / k_dtw_dp   a12 DTW preprocessing and the DP
@@ -353,22 +352,6 @@ __global__ void k_embed(const f16* E, const float* P, const int* tok, const int*
 
 void launch_embed(const f16* E, const float* P, const int* tok, const int* pos, int R, int d, float* x, hipStream_t s) {
   WDR_KLAUNCH(k_embed, dim3(R), dim3(256), 0, s, E, P, tok, pos, d, x);
-  WDR_HIP(hipGetLastError());
-}
-
-__global__ void k_kv_scatter(const f16* qkv, int ldqkv, int d, const int* row_seq, const int* row_pos, f16* kc,
-                             f16* vc, long long seq_stride) {
-  const int r = blockIdx.x;
-  const long long dst = row_seq[r] * seq_stride + (long long)row_pos[r] * d;
-  for (int c = threadIdx.x * 8; c < d; c += blockDim.x * 8) {
-    *(f16x8*)(kc + dst + c) = *(const f16x8*)(qkv + (long long)r * ldqkv + d + c);
-    *(f16x8*)(vc + dst + c) = *(const f16x8*)(qkv + (long long)r * ldqkv + 2 * d + c);
-  }
-}
-
-void launch_kv_scatter(const f16* qkv, int ldqkv, int d, const int* row_seq, const int* row_pos, int R, f16* kc, f16* vc,
-                       long long seq_stride, hipStream_t s) {
-  WDR_KLAUNCH(k_kv_scatter, dim3(R), dim3(64), 0, s, qkv, ldqkv, d, row_seq, row_pos, kc, vc, seq_stride);
   WDR_HIP(hipGetLastError());
 }
 

@@ -53,8 +53,6 @@ void launch_audio_split(const void* raw, int fmt, int C, long long frame0, long 
 void launch_layernorm(const float* x, int ldx, const float* g, const float* b, f16* y, int ldy, int rows, int d,
                       hipStream_t s);
 void launch_embed(const f16* E, const float* P, const int* tok, const int* pos, int R, int d, float* x, hipStream_t s);
-void launch_kv_scatter(const f16* qkv, int ldqkv, int d, const int* row_seq, const int* row_pos, int R, f16* kc, f16* vc,
-                       long long seq_stride, hipStream_t s);
 
 struct LogitsCtl {
   int n_tokens;        // tokens already sampled in this sequence (0 -> initial step)
@@ -162,17 +160,6 @@ struct XAttnArgs {
 constexpr int XATTN_GRP_MAX = 8;   // rows sharing one K/V without row_k
 inline unsigned long long* prof_attach(XAttnArgs& a) { return a.ts = prof_slot(); }
 void launch_xattn(const XAttnArgs& a, hipStream_t s);
-struct CaptureArgs {
-  const f16* q; int ldq;
-  const f16* k; int ldk;
-  const float2* ml;
-  const int* heads;
-  float* out;
-  int slot0, R, Tk;
-  float scale;
-  long long hs = 64;                  // head stride of K (elements)
-};
-void launch_aheads_capture(const CaptureArgs& a, int n_sel, hipStream_t s);
 // decoder rows (rows_forward): the cross-attention partials of the VALU groups and the MFMA
 // tiles of one layer, then the combine of every row
 void launch_xattn_rows(const XAttnArgs& a, hipStream_t s);

@@ -364,6 +364,17 @@ class State {
   // full()'s rule constants for (max_initial_ts, suppress_blank)
   void dbg_logits(const float* logits, int R, const LogitsCtl* ctl, float max_initial_ts, bool suppress_blank,
                   TokenData* out, float* nosp);
+  // dbg_logits, then the beam top-K (logits_topk: out [R][K]) / the sampling distribution
+  // (launch_logits_probs as decode_sample runs it: probs / logprobs [R][n_vocab]) of the same rows
+  void dbg_logits_topk(const float* logits, int R, const LogitsCtl* ctl, float max_initial_ts, bool suppress_blank,
+                       int K, BeamCand* out);
+  void dbg_logits_probs(const float* logits, int R, const LogitsCtl* ctl, float max_initial_ts, bool suppress_blank,
+                        float* probs, float* logprobs);
+  // the first n_rows self-attention cache rows of decoder sequence seq (0 .. 7) of this chain in
+  // every layer, k / v [L][n_rows][d] f16 bits: written from or read into the host arrays
+  void dbg_kv_rows(int seq, int n_rows, bool write, uint16_t* k, uint16_t* v);
+  // kv_reorder with moves (src[i], dst[i]); every dst at most once
+  void dbg_kv_reorder(const int* src, const int* dst, int n, int n_rows);
 
   struct Impl;
 

@@ -1976,6 +1976,60 @@ void State::dbg_logits(const float* logits, int R, const LogitsCtl* ctl, float m
   run_logits(R, ctl, out, nosp);
 }
 
+void State::dbg_logits_topk(const float* logits, int R, const LogitsCtl* ctl, float max_initial_ts,
+                            bool suppress_blank, int K, BeamCand* out) {
+  WDR_CHECK(R >= 1 && R <= NSEQ && K >= 1 && K <= BEAM_KMAX, "dbg_logits_topk: 1..8 rows, K 1..BEAM_KMAX");
+  std::vector<TokenData> td(R);
+  dbg_logits(logits, R, ctl, max_initial_ts, suppress_blank, td.data(), nullptr);
+  logits_topk(R, K, out);
+}
+
+void State::dbg_logits_probs(const float* logits, int R, const LogitsCtl* ctl, float max_initial_ts,
+                             bool suppress_blank, float* probs, float* logprobs) {
+  Impl& m = *m_;
+  WDR_CHECK(R >= 1 && R <= NSEQ, "dbg_logits_probs: 1..8 rows");
+  std::vector<TokenData> td(R);
+  dbg_logits(logits, R, ctl, max_initial_ts, suppress_blank, td.data(), nullptr);
+  launch_logits_probs(m.mb.logits.as<float>(), m.V, m.ctl.as<LogitsCtl>(), m.vids, R, m.work.as<float>(),
+                      m.sprobs.as<float>(), m.slogp.as<float>(), s_);
+  WDR_HIP(wdr_memcpy_async(probs, m.sprobs.p, (size_t)R * m.V * 4, hipMemcpyDeviceToHost, s_));
+  WDR_HIP(wdr_memcpy_async(logprobs, m.slogp.p, (size_t)R * m.V * 4, hipMemcpyDeviceToHost, s_));
+  WDR_HIP(hipStreamSynchronize(s_));
+}
+
+void State::dbg_kv_rows(int seq, int n_rows, bool write, uint16_t* k, uint16_t* v) {
+  Impl& m = *m_;
+  WDR_CHECK(seq >= 0 && seq < NSEQ, "dbg_kv_rows: sequence out of range");
+  WDR_CHECK(n_rows >= 1 && (long long)n_rows * m.d <= m.seq_stride, "dbg_kv_rows: row count out of range");
+  WDR_HIP(hipStreamSynchronize(s_));
+  const size_t n = (size_t)n_rows * m.d;
+  for (int l = 0; l < m.L; ++l) {
+    const size_t off = (size_t)l * ctx_.kv_layer_stride + (size_t)seq * m.seq_stride;
+    if (write) {
+      WDR_HIP(hipMemcpy(m.kc + off, k + l * n, n * 2, hipMemcpyHostToDevice));
+      WDR_HIP(hipMemcpy(m.vc + off, v + l * n, n * 2, hipMemcpyHostToDevice));
+    } else {
+      WDR_HIP(hipMemcpy(k + l * n, m.kc + off, n * 2, hipMemcpyDeviceToHost));
+      WDR_HIP(hipMemcpy(v + l * n, m.vc + off, n * 2, hipMemcpyDeviceToHost));
+    }
+  }
+}
+
+void State::dbg_kv_reorder(const int* src, const int* dst, int n, int n_rows) {
+  Impl& m = *m_;
+  WDR_CHECK(n >= 1 && n <= NSEQ, "dbg_kv_reorder: 1..8 moves");
+  WDR_CHECK(n_rows >= 1 && (long long)n_rows * m.d <= m.seq_stride, "dbg_kv_reorder: row count out of range");
+  std::vector<std::pair<int, int>> moves;
+  unsigned seen = 0;
+  for (int i = 0; i < n; ++i) {
+    WDR_CHECK(src[i] >= 0 && src[i] < NSEQ && dst[i] >= 0 && dst[i] < NSEQ, "dbg_kv_reorder: sequence out of range");
+    WDR_CHECK(!(seen >> dst[i] & 1), "dbg_kv_reorder: a destination named twice");
+    seen |= 1u << dst[i];
+    moves.emplace_back(src[i], dst[i]);
+  }
+  kv_reorder(moves, n_rows);
+}
+
 void State::dtw_capture(const int* toks, int n, float* cap_out) {
   decoder_prefill(toks, n, 0, false, true);
   const size_t A = ctx_.aheads.size();

@@ -704,6 +704,52 @@ def dbg_dequant(fmt, blocks, timing: bool = False):
     return (out.view(np.float16), ms.value) if timing else out.view(np.float16)
 
 
+_U16P, _I32P, _F32P = C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_float)
+
+
+def _h16(a):
+    """A contiguous float16 copy of a, viewed as its bits."""
+    return np.ascontiguousarray(np.asarray(a).astype(np.float16)).view(np.uint16)
+
+
+def dbg_self_attn(q, kc, vc, row_seq, row_pos, n_head: int) -> np.ndarray:
+    """Decode-step self-attention (wdr_dbg_self_attn): q [R][64 H], caches kc / vc [n_seq][T][64 H]
+    (rounded to f16); row r attends over keys 0 .. row_pos[r] of sequence row_seq[r].  Returns
+    [R][64 H] float32.  Out-of-range rows are an error, never a launch."""
+    qb, kb, vb = _h16(q), _h16(kc), _h16(vc)
+    rs, rp = np.ascontiguousarray(row_seq, np.int32), np.ascontiguousarray(row_pos, np.int32)
+    R, d = qb.shape
+    n_seq, T, dk = kb.shape
+    if d != 64 * n_head or dk != d or vb.shape != kb.shape or rs.shape != (R,) or rp.shape != (R,):
+        raise ValueError("dbg_self_attn: q [R][64 H], kc / vc [n_seq][T][64 H], row_seq / row_pos [R]")
+    out = np.zeros((R, d), np.float32)
+    L.check(L.load().wdr_dbg_self_attn(qb.ctypes.data_as(_U16P), kb.ctypes.data_as(_U16P), vb.ctypes.data_as(_U16P),
+                                       n_seq, T, rs.ctypes.data_as(_I32P), rp.ctypes.data_as(_I32P), R, n_head,
+                                       out.ctypes.data_as(_F32P)))
+    return out
+
+
+def dbg_proj_qkv(a, w, bias, row_seq, row_pos, kc, vc):
+    """The decoder's fused Q/K/V projection with the cache-scatter epilogue (wdr_dbg_proj_qkv):
+    a [M][K], w [3 d][K] (rounded to f16), bias [3 d] or None, caches kc / vc [n_seq][T][d] float16.
+    Returns (q [M][d] float32, kc, vc after the launch: float16 copies, the inputs are not touched)."""
+    ab, wb = _h16(a), _h16(w)
+    M, K = ab.shape
+    d = wb.shape[0] // 3
+    kb, vb = _h16(kc).copy(), _h16(vc).copy()
+    n_seq, T, dk = kb.shape
+    rs, rp = np.ascontiguousarray(row_seq, np.int32), np.ascontiguousarray(row_pos, np.int32)
+    if wb.shape != (3 * d, K) or dk != d or vb.shape != kb.shape or rs.shape != (M,) or rp.shape != (M,):
+        raise ValueError("dbg_proj_qkv: a [M][K], w [3 d][K], kc / vc [n_seq][T][d], row_seq / row_pos [M]")
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    q = np.zeros((M, d), np.float32)
+    L.check(L.load().wdr_dbg_proj_qkv(ab.ctypes.data_as(_U16P), wb.ctypes.data_as(_U16P),
+                                      None if b is None else b.ctypes.data_as(_F32P), M, d, K,
+                                      rs.ctypes.data_as(_I32P), rp.ctypes.data_as(_I32P), n_seq, T,
+                                      kb.ctypes.data_as(_U16P), vb.ctypes.data_as(_U16P), q.ctypes.data_as(_F32P)))
+    return q, kb.view(np.float16), vb.view(np.float16)
+
+
 class WhisperContext:
     """transcribe::create_context (src/transcribe.rs:89-166) + its whisper_state."""
 
@@ -901,6 +947,68 @@ class WhisperContext:
                                          f.ctypes.data_as(C.POINTER(C.c_float))))
         return [dict(id=int(ids[r, 0]), tid=int(ids[r, 1]), p=float(f[r, 0]), plog=float(f[r, 1]), pt=float(f[r, 2]),
                      ptsum=float(f[r, 3]), nosp=float(f[r, 4])) for r in range(R)]
+
+    def _rule_args(self, logits, ctls, temps):
+        lg = np.ascontiguousarray(logits, np.float32)
+        R = lg.shape[0]
+        if lg.shape != (R, self.hparams["n_vocab"]) or len(ctls) != R:
+            raise ValueError("logits [R][n_vocab] and R rule states")
+        keys = ("n_tokens", "last_ts", "pen_ts", "has_ts", "seek_delta", "force_kind", "force_tok")
+        ctl = np.ascontiguousarray([[int(c.get(k, 0)) for k in keys] for c in ctls], np.int32)
+        tt = np.ascontiguousarray(temps if temps is not None else [0.0] * R, np.float32)
+        if tt.shape != (R,):
+            raise ValueError("one temperature per row")
+        return lg, R, ctl, tt
+
+    def logits_topk(self, logits, ctls, K: int, temps=None, max_initial_ts: float = 1.0, suppress_blank: bool = True):
+        """The beam-search top-K of rows under the logit rules (wdr_dbg_logits_topk; arguments as
+        logit_rules): (ids [R][K] int32, p [R][K], log p [R][K]); absent candidates id -1, 0, -inf."""
+        lg, R, ctl, tt = self._rule_args(logits, ctls, temps)
+        K = int(K)
+        ids = np.zeros((R, max(K, 1)), np.int32)
+        f = np.zeros((R, max(K, 1), 2), np.float32)
+        L.check(self._lib.wdr_dbg_logits_topk(self.h, lg.ctypes.data_as(_F32P), R, ctl.ctypes.data_as(_I32P),
+                                              tt.ctypes.data_as(_F32P), float(max_initial_ts),
+                                              1 if suppress_blank else 0, K, ids.ctypes.data_as(_I32P),
+                                              f.ctypes.data_as(_F32P)))
+        return ids, f[:, :, 0].copy(), f[:, :, 1].copy()
+
+    def logits_probs(self, logits, ctls, temps=None, max_initial_ts: float = 1.0, suppress_blank: bool = True):
+        """The sampling distribution of rows under the logit rules (wdr_dbg_logits_probs; arguments
+        as logit_rules): (probs, logprobs), each [R][n_vocab] float32."""
+        lg, R, ctl, tt = self._rule_args(logits, ctls, temps)
+        probs, logp = np.zeros_like(lg), np.zeros_like(lg)
+        L.check(self._lib.wdr_dbg_logits_probs(self.h, lg.ctypes.data_as(_F32P), R, ctl.ctypes.data_as(_I32P),
+                                               tt.ctypes.data_as(_F32P), float(max_initial_ts),
+                                               1 if suppress_blank else 0, probs.ctypes.data_as(_F32P),
+                                               logp.ctypes.data_as(_F32P)))
+        return probs, logp
+
+    def kv_rows(self, seq: int, n_rows: int):
+        """The first n_rows self-attention cache rows of decoder sequence seq in every layer
+        (wdr_dbg_kv_rows): (k, v), each [n_text_layer][n_rows][d] float16."""
+        shape = (self.hparams["n_text_layer"], int(n_rows), self.hparams["n_text_state"])
+        k, v = np.zeros(shape, np.uint16), np.zeros(shape, np.uint16)
+        L.check(self._lib.wdr_dbg_kv_rows(self.h, int(seq), int(n_rows), 0, k.ctypes.data_as(_U16P),
+                                          v.ctypes.data_as(_U16P)))
+        return k.view(np.float16), v.view(np.float16)
+
+    def set_kv_rows(self, seq: int, k, v):
+        """Store k / v [n_text_layer][n_rows][d] float16 as the first n_rows cache rows of sequence seq."""
+        k, v = (np.ascontiguousarray(a, np.float16) for a in (k, v))
+        if k.shape != v.shape or k.ndim != 3 or k.shape[0] != self.hparams["n_text_layer"] \
+                or k.shape[2] != self.hparams["n_text_state"]:
+            raise ValueError("k / v [n_text_layer][n_rows][d]")
+        L.check(self._lib.wdr_dbg_kv_rows(self.h, int(seq), k.shape[1], 1, k.view(np.uint16).ctypes.data_as(_U16P),
+                                          v.view(np.uint16).ctypes.data_as(_U16P)))
+
+    def kv_reorder(self, moves, n_rows: int):
+        """The beam reorder (wdr_dbg_kv_reorder): for every (src, dst) in moves sequence dst takes the
+        first n_rows cached rows sequence src held before the call."""
+        src = np.ascontiguousarray([m[0] for m in moves], np.int32)
+        dst = np.ascontiguousarray([m[1] for m in moves], np.int32)
+        L.check(self._lib.wdr_dbg_kv_reorder(self.h, src.ctypes.data_as(_I32P), dst.ctypes.data_as(_I32P), len(moves),
+                                             int(n_rows)))
 
     def batch_step_ms(self, tokens, rows: int, iters: int = 50) -> float:
         """Host ms per multi-chain batched step of `rows` rows on the last encoded window

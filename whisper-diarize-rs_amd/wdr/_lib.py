@@ -193,6 +193,14 @@ _SIGS = {
                                    P(C.c_uint8), P(C.c_uint8), P(C.c_uint8)]),
     "wdr_dbg_attn": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(C.c_uint16), i32, i32, i32, i32, P(f32)]),
     "wdr_dbg_xattn": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(i32), P(i32), i32, i32, i32, i32, P(f32)]),
+    "wdr_dbg_self_attn": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(C.c_uint16), i32, i32, P(i32), P(i32), i32, i32,
+                                    P(f32)]),
+    "wdr_dbg_proj_qkv": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(f32), i32, i32, i32, P(i32), P(i32), i32, i32,
+                                   P(C.c_uint16), P(C.c_uint16), P(f32)]),
+    "wdr_dbg_logits_topk": (C.c_int, [vp, P(f32), i32, P(i32), P(f32), f32, i32, i32, P(i32), P(f32)]),
+    "wdr_dbg_logits_probs": (C.c_int, [vp, P(f32), i32, P(i32), P(f32), f32, i32, P(f32), P(f32)]),
+    "wdr_dbg_kv_rows": (C.c_int, [vp, i32, i32, i32, P(C.c_uint16), P(C.c_uint16)]),
+    "wdr_dbg_kv_reorder": (C.c_int, [vp, P(i32), P(i32), i32, i32]),
 }
 
 _lib = None
