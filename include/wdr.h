@@ -474,10 +474,19 @@ int wdr_dbg_proj(const uint16_t* a_f16, const uint16_t* w_f16, const float* bias
 /* epi | WDR_DBG_PROJ_GEMM1: M > 64 on the register-staged reference tile (k_gemm) whatever the
  * dispatch rule picks -- the tiled GEMM family is bit-identical to it */
 #define WDR_DBG_PROJ_GEMM1 0x800
+/* epi | WDR_DBG_PROJ_PACKED: the weight packed on the GPU into the row kernel's fragment order
+ * (wdr_dbg_pack_rows) and the row kernel run on that layout, any M -- bit for bit the row-major
+ * result (the decoder's weights are stored this way when a model is loaded) */
+#define WDR_DBG_PROJ_PACKED 0x1000
+/* w [N][K] (f16 bits, K % 32 == 0) in fragment order: out [16 ceil(N / 16)][K]; element (n, k) at
+ * 512 ((n / 16) (K / 32) + k / 32) + 8 (16 ((k / 8) & 3) + (n & 15)) + (k & 7), pad rows zero */
+int wdr_dbg_pack_rows(const uint16_t* w_f16, int32_t N, int32_t K, uint16_t* out);
 /* A decoder-rows projection of LayerNorm(x) (x [M][K] f32, gamma / beta [K], K % 128 == 0, K <= 1280): fused = 1
  * normalises inside the row kernel's prologue (every workgroup its own row tiles), 0 = a separate
  * LayerNorm launch into f16 rows first; the two must agree bit for bit at every M (rows_forward
- * fuses up to 64 rows).  epi as wdr_dbg_proj (0 / 1 / 3; out [M][N] f32) */
+ * fuses up to 64 rows).  epi as wdr_dbg_proj (0 / 1 / 3; out [M][N] f32).  fused | 2: the weight in
+ * fragment order (as WDR_DBG_PROJ_PACKED); fused | 4: the rows gathered through the kernel's row map,
+ * output row m from x row M - 1 - m */
 int wdr_dbg_proj_ln(const float* x, const float* gamma, const float* beta, const uint16_t* w_f16, const float* bias,
                     int32_t M, int32_t N, int32_t K, int32_t epi, int32_t fused, float* out);
 int wdr_dbg_attn(const uint16_t* q, const uint16_t* k, const uint16_t* v, int32_t Tq, int32_t Tk, int32_t n_head,
@@ -504,6 +513,10 @@ int wdr_dbg_self_attn(const uint16_t* q, const uint16_t* kc, const uint16_t* vc,
 int wdr_dbg_proj_qkv(const uint16_t* a_f16, const uint16_t* w_f16, const float* bias, int32_t M, int32_t d, int32_t K,
                      const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
                      uint16_t* vc_io, float* q_out);
+/* the same with the weight in fragment order (as WDR_DBG_PROJ_PACKED) */
+int wdr_dbg_proj_qkv_packed(const uint16_t* a_f16, const uint16_t* w_f16, const float* bias, int32_t M, int32_t d,
+                            int32_t K, const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T,
+                            uint16_t* kc_io, uint16_t* vc_io, float* q_out);
 /* wdr_dbg_logits' inputs, then the beam-search top-K of the same rows (k_logits_topk +
  * k_logits_topk_final): ids [R][K], f [R][K][2] = {p, log p}, best first, ties by lower id; a row
  * with fewer than K finite candidates ends with {id -1, p 0, log p -inf} */

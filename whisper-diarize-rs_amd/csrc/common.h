@@ -129,6 +129,10 @@ struct ProjArgs {
   // reduce), so a row's result never depends on how many rows share the launch (the LN
   // prologue normalises each workgroup's own row tiles)
   int rows_mma = 0;
+  // row kernel only: B holds the weights in MFMA fragment order (launch_pack_rows: 1-KB tiles of
+  // 16 rows x 32 k, N padded to a multiple of 16 with zero rows; ldb == K) -- same results, every
+  // wave load one contiguous 1 KB
+  int b_packed = 0;
   // optional row map: A / ln_x row m is row_map[m] (logit rows gathered from the residual stream)
   const int* row_map = nullptr;
 };
@@ -164,6 +168,10 @@ inline unsigned long long* prof_attach(A&) { return nullptr; }
 inline unsigned long long* prof_attach(ProjArgs& a) { return a.ts = prof_slot(); }
 // M <= 64 (or rows_mma) on the row kernel k_skinny, larger M on the MFMA GEMM tiles
 void launch_proj(const ProjArgs& a, hipStream_t s);
+// row-major weights [N][K] f16 (K % 32 == 0) -> the row kernel's fragment order (ProjArgs::
+// b_packed), out of place into packed_rows_elems(N, K) = 16 cdiv(N, 16) K elements
+size_t packed_rows_elems(int N, int K);
+void launch_pack_rows(const f16* w, f16* out, int N, int K, hipStream_t s);
 // re-read the encoder GEMM dispatch knobs (WDR_GEMM*), which launch_proj reads once per process:
 // tools/gemm_bench's per-variant A/B only
 void gemm_knobs_reload();

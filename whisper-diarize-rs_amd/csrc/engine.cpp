@@ -2599,6 +2599,30 @@ int wdr_dbg_proj_fp8(const uint16_t* a16, const uint16_t* w16, const float* bias
   })
 }
 
+// the debug projections' packed form: a's row-major weight packed into `pk` (fragment order,
+// launch_pack_rows) and a pointed at it
+static void dbg_pack(ProjArgs& a, bool packed, DevMem& pk) {
+  if (!packed) return;
+  WDR_CHECK(a.K >= 32 && a.K % 32 == 0, "dbg projection, packed weights: K % 32");
+  pk = DevMem(packed_rows_elems(a.N, a.K) * 2);
+  launch_pack_rows(a.B, pk.as<f16>(), a.N, a.K, nullptr);
+  a.B = pk.as<f16>();
+  a.b_packed = 1;
+}
+
+// a weight [N][K] in the row kernel's fragment order (launch_pack_rows): out [16 cdiv(N, 16)][K]
+int wdr_dbg_pack_rows(const uint16_t* w16, int32_t N, int32_t K, uint16_t* out) {
+  WDR_GUARD({
+    WDR_CHECK(w16 && out && N >= 1 && N <= (1 << 20) && K >= 32 && K <= 8192 && K % 32 == 0, "dbg_pack_rows: bad shape (K % 32)");
+    DevMem dw((size_t)N * K * 2), dp(packed_rows_elems(N, K) * 2);
+    WDR_HIP(hipMemcpy(dw.p, w16, dw.bytes, hipMemcpyHostToDevice));
+    launch_pack_rows(dw.as<f16>(), dp.as<f16>(), N, K, nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    WDR_HIP(hipMemcpy(out, dp.p, dp.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  })
+}
+
 int wdr_dbg_proj(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t N, int32_t K,
                  int32_t epi, float* out) {
   WDR_GUARD({
@@ -2612,13 +2636,18 @@ int wdr_dbg_proj(const uint16_t* a16, const uint16_t* w16, const float* bias, in
     const bool rows = (epi & 0x200) != 0;
     if (epi & 0x400) return fail("WDR_DBG_PROJ_SPLIT: the split-K residual projections were removed (k_skinny runs them whole)");
     const bool gemm_ref = (epi & 0x800) != 0;
+    // epi | WDR_DBG_PROJ_PACKED: the weight packed into fragment order first (launch_pack_rows),
+    // the row kernel reading that layout (ProjArgs::b_packed), any M
+    const bool packed = (epi & 0x1000) != 0;
     epi &= 0xff;
     const bool f16out = epi == EPI_F16 || epi == EPI_F16_GELU;
     std::vector<f16> h16;
     if (!f16out) WDR_HIP(hipMemcpy(dout.p, out, dout.bytes, hipMemcpyHostToDevice));
     ProjArgs a{da.as<f16>(), K, dw.as<f16>(), K, bias ? db.as<float>() : nullptr, dout.p, N, nullptr, 0, M, N, K, epi};
-    a.rows_mma = rows ? 1 : 0;
+    a.rows_mma = rows || packed ? 1 : 0;
     a.gemm_ref = gemm_ref ? 1 : 0;
+    DevMem dpk;
+    dbg_pack(a, packed, dpk);
     launch_proj(a, nullptr);
     WDR_HIP(hipDeviceSynchronize());
     if (f16out) {
@@ -2647,6 +2676,18 @@ int wdr_dbg_proj_ln(const float* x, const float* gamma, const float* beta, const
     if (bias) WDR_HIP(hipMemcpy(db.p, bias, db.bytes, hipMemcpyHostToDevice));
     ProjArgs a{nullptr, K, dw.as<f16>(), K, bias ? db.as<float>() : nullptr, dout.p, N, nullptr, 0, M, N, K, epi};
     a.rows_mma = 1;
+    // fused: bit 0 the fused prologue, bit 1 the weight in fragment order (dbg_pack), bit 2 the
+    // rows gathered through a row map (ProjArgs::row_map; here row m reads x row M - 1 - m)
+    DevMem dpk, dmap;
+    dbg_pack(a, (fused & 2) != 0, dpk);
+    if (fused & 4) {
+      std::vector<int> rm(M);
+      for (int m = 0; m < M; ++m) rm[m] = M - 1 - m;
+      dmap = DevMem((size_t)M * 4);
+      WDR_HIP(hipMemcpy(dmap.p, rm.data(), dmap.bytes, hipMemcpyHostToDevice));
+      a.row_map = dmap.as<int>();
+    }
+    fused &= 1;
     if (fused) {   // rows_forward's fused form (csrc/rows.cpp)
       a.ln_x = dx.as<float>();
       a.ldln = K;
@@ -2821,9 +2862,9 @@ int wdr_dbg_self_attn(const uint16_t* q, const uint16_t* kc, const uint16_t* vc,
 // the decoder's fused QKV projection (row kernel, EPI_QKV_CACHE): Q of every row to q_out, its
 // K / V into cache row (row_seq, row_pos) of the caller's cache arrays (uploaded, updated, copied
 // back).  Rows must name distinct cache rows (two rows writing one would race)
-int wdr_dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t d, int32_t K,
-                     const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
-                     uint16_t* vc_io, float* q_out) {
+static int dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t d, int32_t K,
+                        const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
+                        uint16_t* vc_io, float* q_out, bool packed) {
   WDR_GUARD({
     WDR_CHECK(a16 && w16 && row_seq && row_pos && kc_io && vc_io && q_out, "dbg qkv projection: null argument");
     WDR_CHECK(M >= 1 && M <= 4096 && d >= 64 && d <= 2048 && d % 64 == 0 && d % 8 == 0 && K >= 32 && K <= 8192 &&
@@ -2853,6 +2894,8 @@ int wdr_dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias
     a.row_seq = ds.as<int>();
     a.row_pos = dp.as<int>();
     a.d = d;
+    DevMem dpk;
+    dbg_pack(a, packed, dpk);
     launch_proj(a, nullptr);
     WDR_HIP(hipDeviceSynchronize());
     std::vector<f16> h((size_t)M * d);
@@ -2862,6 +2905,17 @@ int wdr_dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias
     WDR_HIP(hipMemcpy(vc_io, dv.p, cache, hipMemcpyDeviceToHost));
     return 0;
   })
+}
+int wdr_dbg_proj_qkv(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t d, int32_t K,
+                     const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T, uint16_t* kc_io,
+                     uint16_t* vc_io, float* q_out) {
+  return dbg_proj_qkv(a16, w16, bias, M, d, K, row_seq, row_pos, n_seq, T, kc_io, vc_io, q_out, false);
+}
+// the same with the weight packed into fragment order first (dbg_pack)
+int wdr_dbg_proj_qkv_packed(const uint16_t* a16, const uint16_t* w16, const float* bias, int32_t M, int32_t d,
+                            int32_t K, const int32_t* row_seq, const int32_t* row_pos, int32_t n_seq, int32_t T,
+                            uint16_t* kc_io, uint16_t* vc_io, float* q_out) {
+  return dbg_proj_qkv(a16, w16, bias, M, d, K, row_seq, row_pos, n_seq, T, kc_io, vc_io, q_out, true);
 }
 
 static void dbg_ctls(const int32_t* ctl, const float* temperature, int R, std::vector<LogitsCtl>& lc) {

@@ -11,7 +11,9 @@
 //              re-forwards, language detection) and every other projection of <= 64 rows:
 //              16-row MFMA tiles, K split over 8 or 16 waves in a fixed order (optionally a
 //              fused LayerNorm prologue), so a row's result does not depend on the launch's
-//              other rows.  Roofline: HBM (N*K*2 per launch).
+//              other rows.  Roofline: HBM (N*K*2 per launch).  The decoder's weights are stored
+//              in MFMA fragment order (k_pack_rows at load; ProjArgs::b_packed), every wave
+//              load one contiguous 1 KB; the row-major form serves everything else.
 #include "../common.h"
 #include "../prof.h"
 
@@ -1500,7 +1502,14 @@ static uint32_t skinny_ln_lds(int K) {
   return std::max((uint32_t)16 * MT * K * 2, skinny_red_bytes<EPI, MT, NT, W>());
 }
 
-template <int EPI, int MT, int NT, int W = 4, bool LN = false, int UU = 0>
+// PK: the weights in fragment order (ProjArgs::b_packed, k_pack_rows below): 1-KB tiles of 16
+// rows x 32 k, a tile holding the 64 lanes' 16-B B fragments of one MFMA back to back, the tiles
+// of a 16-row strip contiguous along k.  A wave's B load is then one contiguous 1 KB (eight whole
+// 128-B lines) where the row-major form touches 16 weight rows x 64 B -- sixteen half lines, the
+// other halves fetched by another wave.  Same values in the same registers, same k order: the
+// results are bit-identical.  Columns past N read the zero pad rows (row-major: row N - 1 again);
+// they are never stored.
+template <int EPI, int MT, int NT, int W = 4, bool LN = false, int UU = 0, bool PK = false>
 __global__ __launch_bounds__(W * 64) void k_skinny(ProjArgs a) {
   ProfClock prof_clock_(a.ts);   // sampled launches only (csrc/prof.cpp)
   __shared__ float red_s[LN ? 1 : W * MT * NT * 4 * 64];
@@ -1575,9 +1584,15 @@ __global__ __launch_bounds__(W * 64) void k_skinny(ProjArgs a) {
   const f16* brow[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
-    int n = n0 + j * 16 + fr;
-    n = n < a.N ? n : a.N - 1;
-    brow[j] = a.B + (size_t)n * a.ldb + fk;
+    if constexpr (PK) {
+      // strip n0 / 16 + j (the last workgroup of an odd strip count takes the last strip twice)
+      const int strip = min((int)blockIdx.x * NT + j, cdiv(a.N, 16) - 1);
+      brow[j] = a.B + (size_t)strip * a.K * 16 + lane * 8;
+    } else {
+      int n = n0 + j * 16 + fr;
+      n = n < a.N ? n : a.N - 1;
+      brow[j] = a.B + (size_t)n * a.ldb + fk;
+    }
   }
   // U k-steps per batch: all of a batch's fragment loads are issued before its MFMAs, so each
   // wave keeps U*(NT+MT) 16-B loads in flight instead of one dependent round trip per step
@@ -1592,7 +1607,8 @@ __global__ __launch_bounds__(W * 64) void k_skinny(ProjArgs a) {
       const int kk = ok ? k : 0;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const f16x8 t = *(const f16x8*)(brow[j] + kk);
+        // PK: k-step kk / 32 is tile kk / 32 of the strip, 512 f16 each
+        const f16x8 t = *(const f16x8*)(brow[j] + (PK ? kk * 16 : kk));
         bf[u][j] = ok ? t : (f16x8){};
       }
 #pragma unroll
@@ -1774,6 +1790,13 @@ static void launch_rows_epi(const ProjArgs& a, hipStream_t s) {
   const bool ln = a.ln_x != nullptr;
   const bool wide = a.N >= 4096;
   const int prof = PROF_GEMV;   // the "rows" class of bench.py's live roofline (any row count)
+  // one tiling (MT, NT, W, LN, UU) on the weights' layout: fragment order or row-major
+#define WDR_SK_T(...) __VA_ARGS__
+#define WDR_SK(T, G, B, LDS)                                                                      \
+  do {                                                                                            \
+    if (a.b_packed) wdr_launch(prof, bytes, flops, k_skinny<EPI, WDR_SK_T T, true>, G, B, LDS, s, a); \
+    else wdr_launch(prof, bytes, flops, k_skinny<EPI, WDR_SK_T T, false>, G, B, LDS, s, a);       \
+  } while (0)
   if (!wide) {
     // one 16-row tile per workgroup: the row tiles of a column tile re-read its weights from L2.
     // K > 2048 (fc2): 16 waves, each wave's 10 k-steps as ONE batch of loads (8 waves took three
@@ -1787,12 +1810,12 @@ static void launch_rows_epi(const ProjArgs& a, hipStream_t s) {
         // 16.6 us).  Each wave's 10 k-steps as two batches of 5 (10 at MT = 2 spills)
         const int m2 = std::min(mt, rows_mt_max());
         const dim3 g2(cdiv(a.N, 16), cdiv(mt, m2));
-        if (m2 >= 4) wdr_launch(prof, bytes, flops, k_skinny<EPI, 4, 1, 16, false, 2>, g2, dim3(1024), 0, s, a);
-        else if (m2 == 3) wdr_launch(prof, bytes, flops, k_skinny<EPI, 3, 1, 16, false, 5>, g2, dim3(1024), 0, s, a);
-        else wdr_launch(prof, bytes, flops, k_skinny<EPI, 2, 1, 16, false, 5>, g2, dim3(1024), 0, s, a);
+        if (m2 >= 4) WDR_SK((4, 1, 16, false, 2), g2, dim3(1024), 0);
+        else if (m2 == 3) WDR_SK((3, 1, 16, false, 5), g2, dim3(1024), 0);
+        else WDR_SK((2, 1, 16, false, 5), g2, dim3(1024), 0);
         return;
       }
-      wdr_launch(prof, bytes, flops, k_skinny<EPI, 1, 1, 16, false, 12>, dim3(cdiv(a.N, 16), mt), dim3(1024), 0, s, a);
+      WDR_SK((1, 1, 16, false, 12), dim3(cdiv(a.N, 16), mt), dim3(1024), 0);
       return;
     }
     if (!ln && mt > 2 && rows_pair_tiles()) {
@@ -1800,32 +1823,60 @@ static void launch_rows_epi(const ProjArgs& a, hipStream_t s) {
       // WDR_ROWS_MT) row tiles per workgroup, so a column tile's weights are read half as often
       const int m2 = std::min(mt, rows_mt_max());
       const dim3 g2(cdiv(a.N, 16), cdiv(mt, m2));
-      if (m2 >= 5) wdr_launch(prof, bytes, flops, k_skinny<EPI, 5, 1, 8>, g2, dim3(512), 0, s, a);
-      else if (m2 == 4) wdr_launch(prof, bytes, flops, k_skinny<EPI, 4, 1, 8>, g2, dim3(512), 0, s, a);
-      else if (m2 == 3) wdr_launch(prof, bytes, flops, k_skinny<EPI, 3, 1, 8>, g2, dim3(512), 0, s, a);
-      else wdr_launch(prof, bytes, flops, k_skinny<EPI, 2, 1, 8>, g2, dim3(512), 0, s, a);
+      if (m2 >= 5) WDR_SK((5, 1, 8, false, 0), g2, dim3(512), 0);
+      else if (m2 == 4) WDR_SK((4, 1, 8, false, 0), g2, dim3(512), 0);
+      else if (m2 == 3) WDR_SK((3, 1, 8, false, 0), g2, dim3(512), 0);
+      else WDR_SK((2, 1, 8, false, 0), g2, dim3(512), 0);
       return;
     }
     dim3 grid(cdiv(a.N, 16), mt), blk(512);
-    if (ln) wdr_launch(prof, bytes, flops, k_skinny<EPI, 1, 1, 8, true>, grid, blk, skinny_ln_lds<EPI, 1, 1, 8>(a.K), s, a);
-    else wdr_launch(prof, bytes, flops, k_skinny<EPI, 1, 1, 8>, grid, blk, 0, s, a);
+    if (ln) WDR_SK((1, 1, 8, true, 0), grid, blk, (skinny_ln_lds<EPI, 1, 1, 8>(a.K)));
+    else WDR_SK((1, 1, 8, false, 0), grid, blk, 0);
     return;
   }
   // wide N (fc1, logits): 32 columns per workgroup, up to 4 row tiles per workgroup
   const int mtw = std::min(mt, ln ? 2 : 4);
   dim3 grid(cdiv(a.N, 32), cdiv(mt, mtw)), blk(512);
 #define WDR_RW(MTV)                                                                                        \
-  if (ln) wdr_launch(prof, bytes, flops, k_skinny<EPI, MTV, 2, 8, true>, grid, blk, skinny_ln_lds<EPI, MTV, 2, 8>(a.K), s, a); \
-  else wdr_launch(prof, bytes, flops, k_skinny<EPI, MTV, 2, 8>, grid, blk, 0, s, a);
+  if (ln) WDR_SK((MTV, 2, 8, true, 0), grid, blk, (skinny_ln_lds<EPI, MTV, 2, 8>(a.K)));                   \
+  else WDR_SK((MTV, 2, 8, false, 0), grid, blk, 0);
   if (mtw == 1) { WDR_RW(1) }
   else if (mtw == 2) { WDR_RW(2) }
   else if (mtw == 3) { WDR_RW(3) }
   else { WDR_RW(4) }
 #undef WDR_RW
+#undef WDR_SK
+#undef WDR_SK_T
+}
+
+// Row-major weights [N][K] -> fragment order (k_skinny PK): element (n, k) at tile (n / 16, k / 32)
+// of [cdiv(N, 16)][K / 32] 1-KB tiles, inside it at (((k / 8) & 3) * 16 + (n & 15)) * 8 + (k & 7);
+// rows N .. 16 cdiv(N, 16) are zeros.  One thread per 16-B chunk, whole 64-B runs read per row,
+// whole tiles written.  Run once per matrix when a model is loaded.
+__global__ __launch_bounds__(256) void k_pack_rows(const f16* w, f16* out, int N, int K, long long chunks) {
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;   // packed chunk index
+  if (c >= chunks) return;
+  const int kt = K >> 5;
+  const long long tile = c >> 6;
+  const int l = (int)(c & 63);
+  const int n = (int)(tile / kt) * 16 + (l & 15), k = (int)(tile % kt) * 32 + (l >> 4) * 8;
+  f16x8 v = {};
+  if (n < N) v = *(const f16x8*)(w + (size_t)n * K + k);
+  *(f16x8*)(out + c * 8) = v;
+}
+
+size_t packed_rows_elems(int N, int K) { return (size_t)cdiv(N, 16) * 16 * K; }
+
+void launch_pack_rows(const f16* w, f16* out, int N, int K, hipStream_t s) {
+  WDR_CHECK(N >= 1 && K >= 32 && K % 32 == 0 && w != out, "pack rows: K % 32, out of place");
+  const long long chunks = (long long)packed_rows_elems(N, K) / 8;
+  WDR_KLAUNCH(k_pack_rows, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, w, out, N, K, chunks);
+  WDR_HIP(hipGetLastError());
 }
 
 static void launch_rows(const ProjArgs& a, hipStream_t s) {
   WDR_CHECK(a.K % 32 == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0, "row projection: K % 32, lda / ldb % 8");
+  WDR_CHECK(!a.b_packed || a.ldb == a.K, "row projection: packed weights have no row stride (ldb == K)");
   // LN prologue: every workgroup normalises only its own <= 32 rows (any M)
   WDR_CHECK(!a.ln_x || (a.K <= 1280 && a.K % 128 == 0), "row projection LN prologue: K <= 1280, K % 128 == 0");
   WDR_CHECK(a.epi != EPI_QKV_CACHE || (a.kc && a.vc && a.row_seq && a.row_pos && a.d > 0), "qkv-cache epilogue args");
@@ -1848,6 +1899,7 @@ void launch_proj(const ProjArgs& a, hipStream_t s) {
     launch_rows(a, s);
     return;
   }
+  WDR_CHECK(!a.b_packed, "projection: only the row kernel reads fragment-order weights");
   WDR_CHECK(a.K % 8 == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0, "projection: K/lda/ldb must be multiples of 8");
   WDR_CHECK(a.N % GB_N == 0, "gemm: N must be a multiple of 128");
   WDR_CHECK(a.K % GB_K == 0, "gemm: K must be a multiple of 32");

@@ -184,10 +184,12 @@ void rows_forward(const Context& ctx, const RowsIO& io, int R, hipStream_t s, in
   static const int ln_env = getenv("WDR_ROWS_LN_FUSE") ? atoi(getenv("WDR_ROWS_LN_FUSE")) : -1;
   const int fuse_qkv = ln_env >= 0 ? ln_env : 48, fuse_xq = ln_env >= 0 ? ln_env : 64,
             fuse_fc1 = ln_env >= 0 ? ln_env : 24, fuse_logits = ln_env >= 0 ? ln_env : 0;
-  auto P = [&](const f16* A, int lda, const f16* W, const float* b, void* out, int ldo, int N, int K, int epi,
-               const float* lng = nullptr, const float* lnb = nullptr, int fuse_max = 0) {
+  // pk: this matrix's bit of Model::rows_packed (the weights sit in fragment order)
+  auto P = [&](const f16* A, int lda, const f16* W, unsigned pk, const float* b, void* out, int ldo, int N, int K,
+               int epi, const float* lng = nullptr, const float* lnb = nullptr, int fuse_max = 0) {
     ProjArgs a{A, lda, W, K, b, out, ldo, nullptr, 0, R, N, K, epi};
     a.rows_mma = 1;
+    a.b_packed = (md.rows_packed & pk) ? 1 : 0;
     if (lng) {
       if (R <= fuse_max) {
         a.ln_x = io.xd;
@@ -209,7 +211,7 @@ void rows_forward(const Context& ctx, const RowsIO& io, int R, hipStream_t s, in
     const DecLayer& e = md.dec[l];
     f16* kc = io.kc + (size_t)l * io.layer_stride;
     f16* vc = io.vc + (size_t)l * io.layer_stride;
-    ProjArgs q = P(nullptr, d, e.w_qkv, e.b_qkv, io.qkvd, 3 * d, 3 * d, d, EPI_QKV_CACHE, e.ln1_g, e.ln1_b, fuse_qkv);
+    ProjArgs q = P(nullptr, d, e.w_qkv, Model::PK_QKV, e.b_qkv, io.qkvd, 3 * d, 3 * d, d, EPI_QKV_CACHE, e.ln1_g, e.ln1_b, fuse_qkv);
     q.kc = kc;
     q.vc = vc;
     q.seq_stride = io.seq_stride;
@@ -221,8 +223,8 @@ void rows_forward(const Context& ctx, const RowsIO& io, int R, hipStream_t s, in
     // predecessors' keys: causal by position)
     DecSelfArgs sa{io.qkvd, 3 * d, kc, vc, io.seq_stride, d, io.seq, io.pos, io.attd, d, scale};
     launch_dec_self_attn(sa, R, H, s);
-    launch_proj(P(io.attd, d, e.w_o, e.b_o, io.xd, d, d, d, EPI_F32_RESID), s);
-    launch_proj(P(nullptr, d, e.w_xq, e.b_xq, io.qx, d, d, d, EPI_F16, e.ln2_g, e.ln2_b, fuse_xq), s);
+    launch_proj(P(io.attd, d, e.w_o, Model::PK_O, e.b_o, io.xd, d, d, d, EPI_F32_RESID), s);
+    launch_proj(P(nullptr, d, e.w_xq, Model::PK_XQ, e.b_xq, io.qx, d, d, d, EPI_F16, e.ln2_g, e.ln2_b, fuse_xq), s);
     XAttnArgs xa{io.qx, d, nullptr, nullptr, 64, XKV_T, R, H, scale, io.part_o, io.part_ml, io.attd, d};
     xa.row_k = io.xkv;
     xa.layer_off = xkv_k_off(l, H);
@@ -248,14 +250,17 @@ void rows_forward(const Context& ctx, const RowsIO& io, int R, hipStream_t s, in
     }
     if (ctx.aheads_per_layer.size() == (size_t)L) cap_slot0 += (int)ctx.aheads_per_layer[l].size();
     if (l + 1 >= l_stop) return;   // a DTW pass: nothing after this layer's capture matters
-    launch_proj(P(io.attd, d, e.w_xo, e.b_xo, io.xd, d, d, d, EPI_F32_RESID), s);
-    launch_proj(P(nullptr, d, e.w_fc1, e.b_fc1, io.mlpd, 4 * d, 4 * d, d, EPI_F16_GELU, e.ln3_g, e.ln3_b, fuse_fc1), s);
-    launch_proj(P(io.mlpd, 4 * d, e.w_fc2, e.b_fc2, io.xd, d, d, 4 * d, EPI_F32_RESID), s);
+    launch_proj(P(io.attd, d, e.w_xo, Model::PK_XO, e.b_xo, io.xd, d, d, d, EPI_F32_RESID), s);
+    launch_proj(P(nullptr, d, e.w_fc1, Model::PK_FC1, e.b_fc1, io.mlpd, 4 * d, 4 * d, d, EPI_F16_GELU, e.ln3_g, e.ln3_b, fuse_fc1), s);
+    launch_proj(P(io.mlpd, 4 * d, e.w_fc2, Model::PK_FC2, e.b_fc2, io.xd, d, d, 4 * d, EPI_F32_RESID), s);
   }
   if (io.n_logit > 0) {
     // final LayerNorm + logits of the logit rows only, gathered by lrow (compact output)
-    ProjArgs a{nullptr, d, md.tok_emb, d, nullptr, io.logits, io.ldlogits, nullptr, 0, io.n_logit, hp.n_vocab, d, EPI_F32};
+    const bool pk = (md.rows_packed & Model::PK_LOGITS) != 0;   // the packed copy of tok_emb
+    ProjArgs a{nullptr, d, pk ? md.tok_emb_pk : md.tok_emb, d, nullptr, io.logits, io.ldlogits, nullptr, 0, io.n_logit,
+               hp.n_vocab, d, EPI_F32};
     a.rows_mma = 1;
+    a.b_packed = pk ? 1 : 0;
     if (io.n_logit <= fuse_logits) {
       a.ln_x = io.xd;
       a.ldln = d;

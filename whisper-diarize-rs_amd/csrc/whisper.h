@@ -72,6 +72,16 @@ struct Model {
   f16* w_xkv = nullptr;    // [L*2d][d]: per decoder layer cross K rows then cross V rows
   float* b_xkv = nullptr;  // [L*2d]
   f16* tok_emb = nullptr;
+  // Decoder weights in the row kernel's fragment order (ProjArgs::b_packed), packed once when
+  // the model is loaded: bit i of rows_packed says DecLayer matrix i of every layer (PK_QKV ..
+  // PK_FC2) holds packed data IN PLACE -- only rows_forward reads those six -- and PK_LOGITS that
+  // tok_emb_pk is a packed COPY of tok_emb for the logits projection (tok_emb itself stays
+  // row-major: launch_embed gathers rows of it).  WDR_ROWS_PACKED (a mask, read at load; 0: all
+  // row-major, the A/B baseline)
+  enum { PK_QKV = 1, PK_O = 2, PK_XQ = 4, PK_XO = 8, PK_FC1 = 16, PK_FC2 = 32, PK_LOGITS = 64 };
+  unsigned rows_packed = 0;
+  f16* tok_emb_pk = nullptr;
+  DevMem tok_emb_pk_mem;
   float *dec_pos = nullptr, *ln_g = nullptr, *ln_b = nullptr;
   float *mel_filters = nullptr, *hann = nullptr, *cos_tab = nullptr, *sin_tab = nullptr;
   DevMem storage;

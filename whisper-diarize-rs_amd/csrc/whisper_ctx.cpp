@@ -637,8 +637,39 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
     aheads_dev = DevMem(std::max<size_t>(4, flat.size() * 4));
     if (!flat.empty()) WDR_HIP(wdr_memcpy_async(aheads_dev.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice, s));
   }
+  // ---- decoder row projections: weights into the row kernel's fragment order (whisper.h
+  // Model::rows_packed), whatever route filled them (synthetic, f16 / f32 file, dequantized
+  // blocks).  In place through one scratch buffer the size of the largest matrix; the logits get a
+  // packed copy of tok_emb.  Default mask: the shapes where the packed form measured not slower
+  // alone at any row count (profiles/r07/rows_bench_packed.txt)
+  DevMem pscratch;
+  {
+    const char* pe = getenv("WDR_ROWS_PACKED");
+    m.rows_packed = pe ? (unsigned)strtoul(pe, nullptr, 0) & 0x7f : 0x7fu;
+    if (m.rows_packed & 0x3f) pscratch = DevMem((size_t)4 * dt * dt * 2);
+    auto pack = [&](f16* w, int N, int K) {
+      launch_pack_rows(w, pscratch.as<f16>(), N, K, s);   // N % 16 == 0 (d % 128): no pad rows
+      WDR_HIP(wdr_memcpy_async(w, pscratch.p, (size_t)N * K * 2, hipMemcpyDeviceToDevice, s));
+    };
+    for (int i = 0; i < L; ++i) {
+      const DecLayer& e = m.dec[i];
+      if (m.rows_packed & Model::PK_QKV) pack(e.w_qkv, 3 * dt, dt);
+      if (m.rows_packed & Model::PK_O) pack(e.w_o, dt, dt);
+      if (m.rows_packed & Model::PK_XQ) pack(e.w_xq, dt, dt);
+      if (m.rows_packed & Model::PK_XO) pack(e.w_xo, dt, dt);
+      if (m.rows_packed & Model::PK_FC1) pack(e.w_fc1, 4 * dt, dt);
+      if (m.rows_packed & Model::PK_FC2) pack(e.w_fc2, dt, 4 * dt);
+    }
+    if (m.rows_packed & Model::PK_LOGITS) {
+      m.tok_emb_pk_mem = DevMem(packed_rows_elems(hp.n_vocab, dt) * 2);
+      m.tok_emb_pk = m.tok_emb_pk_mem.as<f16>();
+      m.weight_bytes += m.tok_emb_pk_mem.bytes;
+      launch_pack_rows(m.tok_emb, m.tok_emb_pk, hp.n_vocab, dt, s);
+    }
+  }
   WDR_HIP(hipStreamSynchronize(s));
   qstage = DevMem();
+  pscratch = DevMem();   // freed under hip_alloc_mutex (DevMem)
   {
     // KV pool for the decode chains of every State of this context (multi-chain pipeline)
     const char* e = getenv("WDR_DECODE_CHAINS");

@@ -729,9 +729,10 @@ def dbg_self_attn(q, kc, vc, row_seq, row_pos, n_head: int) -> np.ndarray:
     return out
 
 
-def dbg_proj_qkv(a, w, bias, row_seq, row_pos, kc, vc):
+def dbg_proj_qkv(a, w, bias, row_seq, row_pos, kc, vc, packed=False):
     """The decoder's fused Q/K/V projection with the cache-scatter epilogue (wdr_dbg_proj_qkv):
     a [M][K], w [3 d][K] (rounded to f16), bias [3 d] or None, caches kc / vc [n_seq][T][d] float16.
+    packed: the weight in the row kernel's fragment order (wdr_dbg_proj_qkv_packed).
     Returns (q [M][d] float32, kc, vc after the launch: float16 copies, the inputs are not touched)."""
     ab, wb = _h16(a), _h16(w)
     M, K = ab.shape
@@ -743,10 +744,10 @@ def dbg_proj_qkv(a, w, bias, row_seq, row_pos, kc, vc):
         raise ValueError("dbg_proj_qkv: a [M][K], w [3 d][K], kc / vc [n_seq][T][d], row_seq / row_pos [M]")
     b = None if bias is None else np.ascontiguousarray(bias, np.float32)
     q = np.zeros((M, d), np.float32)
-    L.check(L.load().wdr_dbg_proj_qkv(ab.ctypes.data_as(_U16P), wb.ctypes.data_as(_U16P),
-                                      None if b is None else b.ctypes.data_as(_F32P), M, d, K,
-                                      rs.ctypes.data_as(_I32P), rp.ctypes.data_as(_I32P), n_seq, T,
-                                      kb.ctypes.data_as(_U16P), vb.ctypes.data_as(_U16P), q.ctypes.data_as(_F32P)))
+    fn = L.load().wdr_dbg_proj_qkv_packed if packed else L.load().wdr_dbg_proj_qkv
+    L.check(fn(ab.ctypes.data_as(_U16P), wb.ctypes.data_as(_U16P), None if b is None else b.ctypes.data_as(_F32P), M, d, K,
+               rs.ctypes.data_as(_I32P), rp.ctypes.data_as(_I32P), n_seq, T, kb.ctypes.data_as(_U16P),
+               vb.ctypes.data_as(_U16P), q.ctypes.data_as(_F32P)))
     return q, kb.view(np.float16), vb.view(np.float16)
 
 

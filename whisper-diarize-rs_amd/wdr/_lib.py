@@ -197,6 +197,9 @@ _SIGS = {
                                     P(f32)]),
     "wdr_dbg_proj_qkv": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(f32), i32, i32, i32, P(i32), P(i32), i32, i32,
                                    P(C.c_uint16), P(C.c_uint16), P(f32)]),
+    "wdr_dbg_proj_qkv_packed": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(f32), i32, i32, i32, P(i32), P(i32), i32,
+                                          i32, P(C.c_uint16), P(C.c_uint16), P(f32)]),
+    "wdr_dbg_pack_rows": (C.c_int, [P(C.c_uint16), i32, i32, P(C.c_uint16)]),
     "wdr_dbg_logits_topk": (C.c_int, [vp, P(f32), i32, P(i32), P(f32), f32, i32, i32, P(i32), P(f32)]),
     "wdr_dbg_logits_probs": (C.c_int, [vp, P(f32), i32, P(i32), P(f32), f32, i32, P(f32), P(f32)]),
     "wdr_dbg_kv_rows": (C.c_int, [vp, i32, i32, i32, P(C.c_uint16), P(C.c_uint16)]),
