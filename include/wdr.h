@@ -377,6 +377,14 @@ int wdr_dbg_set_early_fixup(wdr_context* c, int32_t mode);
 /* test seam: the diarization contractions on the f32 MFMA kernel (1, default) or the VALU f32
  * kernel (0) for every later launch in the process */
 int wdr_dbg_set_gemm32(int32_t mfma);
+/* test seam: the encoder GEMM dispatch plan of a projection of M > 64 rows (csrc/gemm_plan.h) --
+ * what launch_proj (fp8 = 0) / launch_proj_fp8 (fp8 = 1) launches for the shape.  knobs null: the
+ * process's WDR_GEMM* values; else int32[7] {WDR_GEMM1, WDR_GEMM4, WDR_GEMM4_GM, WDR_GEMM5,
+ * WDR_GEMM5_WIDE, WDR_GEMM8N, WDR_GEMM_CUS} as the variables would be set.  plan_out[4] = {kernel
+ * (0 k_gemm, 1 k_gemm2, 2 k_gemm4, 3 k_gemm5, 4 k_gemm8, 5 k_gemm8n), grid x, grid y, dynamic LDS
+ * bytes}.  Host arithmetic only: never touches the GPU. */
+int wdr_dbg_gemm_plan(int32_t fp8, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t ldo, int32_t d,
+                      int32_t gemm_ref, const int32_t* knobs, int32_t* plan_out /* [4] */);
 int wdr_context_stage_times(wdr_context* c, wdr_stage_times* out);
 int wdr_context_hparams(wdr_context* c, int32_t* out /* [10] */);
 

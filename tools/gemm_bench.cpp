@@ -58,20 +58,25 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&a));
   CK(hipEventCreate(&b));
   std::vector<float> ref, r;
-  const char* vname[6] = {"gemm ", "gemm2", "gemm3", "gemm4", "gemm5", "g4gm8"};
+  // A/B variants of the dispatch knobs (csrc/gemm_plan.h); every line prints the kernel the plan names
+  //   0: WDR_GEMM1=1 (k_gemm, the reference of the cross-check)    1: WDR_GEMM4=0 (k_gemm2 / k_gemm)
+  //   2: WDR_GEMM4=1 WDR_GEMM5_WIDE=0 (k_gemm4 on every shape it takes)   3: the default dispatch
+  //   4: WDR_GEMM5=1 (the narrow shapes on k_gemm5 too)   5: variant 2 with WDR_GEMM4_GM=8
+  const char* vname[6] = {"gemm1", "g4off", "g4on ", "deflt", "gemm5", "g4gm8"};
+  const char* kname[6] = {"k_gemm", "k_gemm2", "k_gemm4", "k_gemm5", "k_gemm8", "k_gemm8n"};
   for (const Shape& sh : shapes) {
     for (int variant = 0; variant < 6; ++variant) {
-      // 0: k_gemm (register staging, WDR_GEMM1=1); 1: k_gemm2 / k_gemm (WDR_GEMM3=0);
-      // 2: k_gemm3 / k_gemm2 (256 x 256 tiles where the shape allows); 3: k_gemm4 (ping-pong)
-      unsetenv("WDR_GEMM1");
-      unsetenv("WDR_GEMM3");
-      // 3: k_gemm4 forced on every shape; 4: the default dispatch (k_gemm5 on the narrow shapes)
-      setenv("WDR_GEMM4", variant == 3 || variant == 5 ? "1" : variant == 4 ? "-1" : "0", 1);
-      setenv("WDR_GEMM5", variant == 3 ? "0" : "1", 1);
-      setenv("WDR_GEMM4_GM", variant == 5 ? "8" : "4", 1);
+      for (const char* k : {"WDR_GEMM1", "WDR_GEMM4", "WDR_GEMM4_GM", "WDR_GEMM5", "WDR_GEMM5_WIDE"}) unsetenv(k);
       if (variant == 0) setenv("WDR_GEMM1", "1", 1);
-      if (variant == 1) setenv("WDR_GEMM3", "0", 1);
+      if (variant == 1) setenv("WDR_GEMM4", "0", 1);
+      if (variant == 2 || variant == 5) {
+        setenv("WDR_GEMM4", "1", 1);
+        setenv("WDR_GEMM5_WIDE", "0", 1);
+      }
+      if (variant == 4) setenv("WDR_GEMM5", "1", 1);
+      if (variant == 5) setenv("WDR_GEMM4_GM", "8", 1);
       gemm_knobs_reload();   // launch_proj reads the knobs once per process
+      const char* kernel = kname[gemm_plan(GemmShape{M, sh.N, sh.K, sh.epi, sh.N, 0, false, false}, gemm_knobs()).kernel];
       // EPI_F32 into a zeroed buffer for the cross-check (the timed runs use the real epilogue)
       const size_t on = (size_t)M * sh.N;
       if (sh.N <= 5120) {
@@ -108,11 +113,16 @@ int main(int argc, char** argv) {
       float ms = 0;
       CK(hipEventElapsedTime(&ms, a, b));
       const double us = ms * 1e3 / reps, tf = 2.0 * M * sh.N * sh.K / (us * 1e-6) / 1e12;
-      printf("%-20s %s M=%d N=%5d K=%4d  %9.1f us  %7.1f TFLOP/s\n", sh.name, vname[variant], M, sh.N, sh.K, us, tf);
+      printf("%-20s %s %-8s M=%d N=%5d K=%4d  %9.1f us  %7.1f TFLOP/s\n", sh.name, vname[variant], kernel, M, sh.N, sh.K, us,
+             tf);
     }
   }
   {
-    // fp8 MX encoder GEMMs (BASELINE configs[4], k_gemm8): operands quantised once (launch_quant_f8),
+    // the f16 loop's last variant is still set: back to the default knobs (the fp8 launcher reads
+    // WDR_GEMM4_GM and WDR_GEMM8N through the same reload)
+    for (const char* k : {"WDR_GEMM1", "WDR_GEMM4", "WDR_GEMM4_GM", "WDR_GEMM5", "WDR_GEMM5_WIDE"}) unsetenv(k);
+    gemm_knobs_reload();
+    // fp8 MX encoder GEMMs (BASELINE configs[4], k_gemm8 / k_gemm8n): operands quantised once (launch_quant_f8),
     // the production epilogues (fc1: GELU written as the e4m3 fc2 operand); relative error of the
     // f32 product against the f16 kernel's
     const int mp = (M + 255) / 256 * 256;
@@ -163,8 +173,9 @@ int main(int argc, char** argv) {
       float ms = 0;
       CK(hipEventElapsedTime(&ms, a, b));
       const double us = ms * 1e3 / reps, tf = 2.0 * M * sh.N * sh.K / (us * 1e-6) / 1e12;
-      printf("%-20s fp8mx M=%d N=%5d K=%4d  %9.1f us  %7.1f TFLOP/s  (rel. err vs f16 %.4f)\n", sh.name, M, sh.N, sh.K,
-             us, tf, std::sqrt(num / std::max(den, 1e-30)));
+      const char* kernel = kname[gemm_plan(GemmShape{M, sh.N, sh.K, epi, sh.N, 0, false, true}, gemm_knobs()).kernel];
+      printf("%-20s fp8mx %-8s M=%d N=%5d K=%4d  %9.1f us  %7.1f TFLOP/s  (rel. err vs f16 %.4f)\n", sh.name, kernel, M, sh.N,
+             sh.K, us, tf, std::sqrt(num / std::max(den, 1e-30)));
     }
   }
   {

@@ -9,6 +9,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "gemm_plan.h"   // Epi, the encoder GEMM tile constants, knobs and dispatch rule
+
 namespace wdr {
 
 struct HipError : std::runtime_error {
@@ -33,20 +35,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Epilogue selectors for the projection kernels (GEMM / GEMV).
-enum Epi : int {
-  EPI_F16 = 0,          // out16 = acc + bias
-  EPI_F16_GELU = 1,     // out16 = gelu_tanh(acc + bias)
-  EPI_F32_RESID = 2,    // out32 += acc + bias          (pre-LN residual stream update)
-  EPI_F32 = 3,          // out32 = acc + bias
-  EPI_F32_GELU_POS = 4, // out32 = gelu_tanh(acc + bias) + pos[row % pos_rows]  (conv2 + positional)
-  EPI_QKV_CACHE = 5,    // cols [0,d) -> out16 (Q); [d,2d) / [2d,3d) -> K / V self-attention cache rows
-  EPI_XKV = 6,          // cross K/V of all layers (N = L*2d) into head-major slots (XKV_* below):
-                        // row = window*1500 + key -> slot out + window*seq_stride
-  EPI_F8_GELU = 7       // fp8 GEMM only: out8 = e4m3(gelu_tanh(acc + bias)) with MX scales o_sc
-                        // (the encoder fc1 -> fc2 operand, Fp8Operand layout)
-};
 
 // Cross-K/V slot layout (one per encoded 30-s window): head-major [L][2][H][1500][64] f16, so
 // one head's keys (or values) of one layer are 192 KB contiguous -- a cross-attention chunk of
@@ -172,9 +160,6 @@ void launch_proj(const ProjArgs& a, hipStream_t s);
 // b_packed), out of place into packed_rows_elems(N, K) = 16 cdiv(N, 16) K elements
 size_t packed_rows_elems(int N, int K);
 void launch_pack_rows(const f16* w, f16* out, int N, int K, hipStream_t s);
-// re-read the encoder GEMM dispatch knobs (WDR_GEMM*), which launch_proj reads once per process:
-// tools/gemm_bench's per-variant A/B only
-void gemm_knobs_reload();
 // fp8 MX encoder GEMM (BASELINE configs[4], k_gemm8): ProjArgs::A8 / B8 / a_sc / b_sc, M > 64,
 // N % 256 == 0, K % 128 == 0; epilogues as launch_proj plus EPI_F8_GELU
 void launch_proj_fp8(const ProjArgs& a, hipStream_t s);

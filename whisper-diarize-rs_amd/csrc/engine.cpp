@@ -2281,6 +2281,21 @@ int wdr_dbg_set_gemm32(int32_t mfma) {
   })
 }
 
+int wdr_dbg_gemm_plan(int32_t fp8, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t ldo, int32_t d,
+                      int32_t gemm_ref, const int32_t* knobs, int32_t* plan_out) {
+  WDR_GUARD({
+    if (M <= 64 || N <= 0 || K <= 0 || !plan_out) return fail("gemm plan: M > 64, N, K > 0 and an output");
+    GemmKnobs k = gemm_knobs();
+    if (knobs) k = GemmKnobs{knobs[0], knobs[1], knobs[2], knobs[3], knobs[4], knobs[5], knobs[6]};
+    const GemmPlan p = gemm_plan(GemmShape{M, N, K, epi, ldo, d, gemm_ref != 0, fp8 != 0}, k);
+    plan_out[0] = p.kernel;
+    plan_out[1] = p.grid_x;
+    plan_out[2] = p.grid_y;
+    plan_out[3] = (int32_t)p.lds;
+    return 0;
+  })
+}
+
 int wdr_context_set_encoder_fp8(wdr_context* c, int8_t on) {
   WDR_GUARD({
     WDR_USE(ctx, c);

@@ -24,7 +24,7 @@ namespace wdr {
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int GB_M = 128, GB_N = 128, GB_K = 32;
+// tile constants (GB_*, G2_BK, G3_*, G8_BK) and the ping-pong kernels' LDS sizes: csrc/gemm_plan.h
 constexpr int GLDS = GB_K + 8;   // LDS row stride in halfs (80 B): conflict-free b128 fragment reads
 
 template <int EPI>
@@ -207,18 +207,20 @@ __global__ __launch_bounds__(256, 2) void k_gemm(ProjArgs a) {
 // row r sits at chunk c ^ ((r >> 1) & 7).  Workgroups are remapped so that each XCD owns a
 // contiguous run of tiles (row-major over N tiles): the A rows and B columns a tile reuses stay
 // in that XCD's L2.
-constexpr int G2_BK = 64;
 __device__ __forceinline__ int g2_swz(int r, int c) { return c ^ ((r >> 1) & 7); }
+// XCD-aware tile order (bijective for any tile count): workgroup `orig` of `nwg` runs on XCD
+// orig % 8; XCD x takes the x-th contiguous run of tile ids
+__device__ __forceinline__ int xcd_tile_id(int orig, int nwg) {
+  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+}
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void k_gemm2(ProjArgs a) {
   ProfClock prof_clock_(a.ts);   // sampled launches only (csrc/prof.cpp)
   __shared__ __attribute__((aligned(16))) f16 lds[2][2][GB_M * G2_BK];   // [buf][A,B][128 x 64]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  // XCD-aware tile order (bijective for any tile count)
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+  const int id = xcd_tile_id(blockIdx.x, gridDim.x);
   const int ntn = a.N / GB_N;
   const int bm = id / ntn, bn = id % ntn;
   const int wr = wid >> 1, wc = wid & 1;
@@ -303,191 +305,164 @@ __global__ __launch_bounds__(256, 2) void k_gemm2(ProjArgs a) {
 }
 
 
-// ---------------------------------------------------------------- MFMA GEMM, 256 x 256 tile
-// The big encoder GEMMs (M = windows x 1500 > 2048, N % 256 == 0): 256 x 256 block tile, BK 64,
-// 8 waves (2 along M x 4 along N) of 128 x 64 outputs, v_mfma_f32_16x16x32_f16 (8 x 4
-// accumulator tiles per wave: 128 acc registers), one workgroup per CU.  Operand tiles are
-// staged by global_load_lds into two LDS buffers (2 x (32 + 32) KB = 128 KB, one dynamic LDS
-// array); lane-linear images (8 rows x 128 B per wave-instruction) with the g2_swz XOR applied to
+// ---------------------------------------------------------------- MFMA GEMM, ping-pong tiles
+// The big encoder GEMMs: a 256-row block tile of 256 (k_gemm4, k_gemm8) or 128 (k_gemm5,
+// k_gemm8n) columns, 8 waves (2 along M x 4 along N: 128 x 64 or 128 x 32 outputs each), one
+// workgroup per CU, f16 (v_mfma_f32_16x16x32_f16, the k order of k_gemm, so bit-identical to it)
+// or block-scaled fp8 operands.  Two schedules: four phases per K-tile on the 256 x 256 tile
+// (gemm_pp4_tile: k_gemm4; written out for fp8 in gemm8_tile), two on the 256 x 128 tile
+// (gemm_pp2_tile: k_gemm5; gemm8n_tile).  A K-tile is 128 B per row for both types (64 f16, 128
+// fp8), so the LDS images and the staging are the same byte for byte.
+//
+// LDS: the tile of each operand is cut into the half-tile images a phase reads, 128 rows x 128 B
+// (16 KB) each -- AH[h] = rows 64h..64h+63 of both wave groups; 256 columns: BH[h] = columns
+// 32h..32h+31 of every wave, 128 columns: BT, all 128 B rows -- two buffers of them in one
+// dynamic array.  An image is lane-linear LDS-DMA pieces of 8 rows with the g2_swz XOR applied to
 // the global source address, so the 16-row fragment reads (ds_read_b128) are conflict-free.
-// The loads of tile k+1 are issued before tile k's MFMAs and retired once per K-tile by a
-// counted wait + a raw s_barrier (no __syncthreads fence that would drain them early).
-// Twice the output per staged byte of k_gemm2 (128 x 128) and 4x the MFMAs per barrier.
-constexpr int G3_M = 256, G3_N = 256, G3_BK = 64;
-constexpr uint32_t G3_LDS = 2u * 2u * G3_M * G3_BK * 2u;   // bytes
+constexpr int G4_HALF = 128 * 64;   // halfs per half-tile image
+static_assert(G4_LDS == 2u * 4u * G4_HALF * 2u && G5_LDS == 2u * 3u * G4_HALF * 2u, "gemm_plan.h: LDS of k_gemm4 / k_gemm5");
 
-template <int EPI>
-__global__ __launch_bounds__(512, 1) void k_gemm3(ProjArgs a) {
-  ProfClock prof_clock_(a.ts);   // sampled launches only (csrc/prof.cpp)
-  extern __shared__ __attribute__((aligned(16))) f16 lds3[];   // [buf][A, B][256 x 64]
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
-  const int ntn = a.N / G3_N;
-  const int bm = id / ntn, bn = id % ntn;
-  const int wm = wid >> 2, wn = wid & 3;
-  // DMA blocks of this wave: block j = wid * 4 + jj holds rows 8 j .. 8 j + 7 of each operand
-  const f16* ga[4];
-  const f16* gb[4];
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    const int row = (wid * 4 + jj) * 8 + (lane >> 3);
-    const int c = g2_swz(row, lane & 7);
-    int gm = bm * G3_M + row;
-    gm = gm < a.M ? gm : a.M - 1;
-    ga[jj] = a.A + (size_t)gm * a.lda + c * 8;
-    gb[jj] = a.B + (size_t)(bn * G3_N + row) * a.ldb + c * 8;
-  }
-  constexpr int OP = G3_M * G3_BK;   // halfs per operand image
-  auto stage = [&](int buf, int k0) {
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      __builtin_amdgcn_global_load_lds((const void*)(ga[jj] + k0), (void*)(lds3 + (buf * 2 + 0) * OP + (wid * 4 + jj) * 512),
-                                       16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(gb[jj] + k0), (void*)(lds3 + (buf * 2 + 1) * OP + (wid * 4 + jj) * 512),
-                                       16, 0, 0);
-    }
-  };
-  const int nk = a.K / G3_BK;
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fq = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) stage(cur ^ 1, (kt + 1) * G3_BK);
-    const f16* As = lds3 + (cur * 2 + 0) * OP;
-    const f16* Bs = lds3 + (cur * 2 + 1) * OP;
-#pragma unroll
-    for (int ks = 0; ks < G3_BK / 32; ++ks) {
-      const int c = ks * 4 + fq;   // logical 16-B chunk: k = 8 fq .. 8 fq + 7 of this 32-deep step
-      f16x8 bf[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = wn * 64 + j * 16 + fr;
-        bf[j] = *(const f16x8*)(Bs + r * G3_BK + g2_swz(r, c) * 8);
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int r = wm * 128 + i * 16 + fr;
-        const f16x8 af = *(const f16x8*)(As + r * G3_BK + g2_swz(r, c) * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    // own loads of tile k+1 landed and own reads of tile k retired; the barrier then publishes
-    // every wave's loads and frees buffer `cur` for the next stage
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = bm * G3_M + wm * 128 + i * 16 + fq * 4 + r;
-        const int col = bn * G3_N + wn * 64 + j * 16 + fr;
-        epi_store<EPI>(a, row, col, acc[i][j][r]);
-      }
-}
-
-
-// ---------------------------------------------------------------- MFMA GEMM, 256 x 256 ping-pong
-// k_gemm3's tile and wave layout (8 waves: 2 along M x 4 along N, 128 x 64 outputs each,
-// v_mfma_f32_16x16x32_f16, the same k order, so bit-identical to k_gemm) in a phased schedule:
-//  * a K-tile (BK 64) is four phases, one output quadrant each -- Q(a, b) = the wave's rows
-//    64a..64a+63 x columns 32b..32b+31, 16 MFMAs over the tile's 64 k -- in the order Q00, Q01,
-//    Q11, Q10, so a phase reads 12, 4, 8 or 4 fragments (A kept from Q00 to Q01, B1 from Q01 to
-//    Q11; B0 re-read for Q10);
-//  * a phase is {LDS fragment reads + one half-tile of LDS-DMA staging} barrier {16 MFMAs}
-//    barrier, and waves 4-7 run one barrier behind waves 0-3: the two waves of every SIMD
-//    alternate, one multiplying while the other reads and stages (a ping-pong on the matrix pipe);
-//  * the LDS tile of each operand is cut into the halves the quadrants read -- AH[a] = rows
-//    64a..64a+63 of both wave groups, BH[b] = columns 32b..32b+31 of every wave -- so a half is
-//    restaged one phase after its last read: BH0 of tile t+1 in phase 1 of tile t, AH0 / BH1 /
-//    AH1 of tile t+2 in phases 2 / 3 / 4 (two LDS buffers, two tiles in flight);
-//  * one counted wait per tile (vmcnt(6): the three half-tiles staged after BH0 of tile t+1 stay
-//    in flight across the barriers), raw s_barrier, all LDS in one dynamic array.
-// Image: 128 rows x 128 B per half, lane-linear LDS-DMA pieces of 8 rows, g2_swz on the source.
-constexpr int G4_HALF = 128 * 64;                   // halfs per half-tile image
-constexpr uint32_t G4_LDS = 2u * 4u * G4_HALF * 2u;   // 2 buffers x {AH0, AH1, BH0, BH1}: 128 KB
-
-template <int EPI>
-__device__ __forceinline__ void gemm4_tile(const ProjArgs& a, f16* lds4, int orig, int nwg) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
-  const int ntn = a.N / G3_N;
-  int bm = id / ntn, bn = id % ntn;
+// tile (bm, bn) of workgroup-order index orig of nwg: the XCD order, then (ProjArgs::tile_gm > 1)
+// grouped -- consecutive ids (one XCD's concurrent workgroups) cover tile_gm row tiles x a few
+// column tiles, so the K-slices they stage are shared through that XCD's L2
+template <int TN>
+__device__ __forceinline__ void pp_tile_order(const ProjArgs& a, int orig, int nwg, int& bm, int& bn) {
+  const int id = xcd_tile_id(orig, nwg);
+  const int ntn = a.N / TN;
+  bm = id / ntn, bn = id % ntn;
   if (a.tile_gm > 1) {
-    // grouped order: consecutive ids (one XCD's concurrent workgroups) cover tile_gm row tiles
-    // x a few column tiles, so the K-slices they stage are shared through that XCD's L2
     const int ntm = cdiv(a.M, G3_M), gsz = a.tile_gm * ntn, g = id / gsz, m0 = g * a.tile_gm;
     const int gm = min(a.tile_gm, ntm - m0), l = id - g * gsz;
     bm = m0 + l % gm;
     bn = l / gm;
   }
-  const int grp = wid >> 2, wn = wid & 3;
-  // staging: wave w writes pieces 2w, 2w+1 (8 image rows each) of every half-tile
-  //   AH[h] image row q -> A row bm*256 + (q >> 6)*128 + 64h + (q & 63)
-  //   BH[h] image row q -> B row bn*256 + (q >> 5)*64 + 32h + (q & 31)
-  // as buffer-resource DMA (buffer_load_dwordx4 ... lds): the piece's row base and k0 a
-  // wave-uniform scalar offset, one loop-invariant 32-bit lane offset per piece jj (row lane/8,
-  // g2_swz chunk (lane & 7) ^ ((4 jj + lane/16) & 7) -- wid drops out of the swizzle).  No VGPR an
-  // LDS DMA reads is ever rewritten: hipcc treats those operands like store data and waits
-  // vmcnt(0) before redefining one, which with per-K-tile 64-bit addresses put a full drain of
-  // the two tiles in flight at the head of every K-tile (round 4's k_gemm4 carried it).  Rows
-  // past M read zeros (the descriptor's bounds) and are never stored.
-  // A: the descriptor starts at the tile's first row and ends at row M (rows past it read zeros:
-  // the buffer range check covers the VGPR offset, which carries the row), k0 in the scalar offset
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.A + (size_t)bm * G3_M * a.lda), (short)0, max(0, a.M - bm * G3_M) * a.lda * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)a.B, (short)0, a.N * a.ldb * 2, 0x00020000);
-  uint32_t offa[2][2], offb[2];   // offa[half][jj]: the row inside the tile and the chunk
+}
+
+// Staging of the half-tile images (every ping-pong kernel, f16 and fp8).  Wave w writes pieces
+// 2w, 2w+1 (8 image rows each) of every image:
+//   AH[h] image row q -> A row bm*256 + (q >> 6)*128 + 64h + (q & 63)
+//   BH[h] image row q -> B row bn*256 + (q >> 5)*64 + 32h + (q & 31);   BT row q -> B row bn*128 + q
+// as buffer-resource DMA (buffer_load_dwordx4 ... lds): the piece's row base and k0 are a
+// wave-uniform scalar offset, a lane adds one loop-invariant 32-bit offset per piece jj -- its row
+// lane/8 and its g2_swz chunk ((lane & 7) ^ ((4 jj + lane/16) & 7): wid drops out of the swizzle).
+// No VGPR an LDS DMA reads is ever rewritten: hipcc treats those operands like store data and puts
+// an s_waitcnt vmcnt(0) in front of any redefinition, which with per-K-tile 64-bit addresses sat at
+// the head of every K-tile and drained the two tiles in flight (round 4's k_gemm4 carried it).
+// A's descriptor starts at the tile's first row and ends at row M: rows past M read zeros (the
+// buffer range check covers the VGPR offset, which carries the row) and are never stored.
+//
+// On the cut of this code.  hipcc's scalar scheduling and register numbering of these kernels
+// follow how the source is cut, not only what it computes: the stage / read closures stay in the
+// schedules (where the kernels always had them) and call value-returning helpers, and the
+// descriptors, lane offsets and fragments are separate locals declared in the kernels' old order.
+// Helpers that fill arrays through references, one object holding all of a tile's state, or a
+// shared epilogue / tile-loop function each compile to the same K loop behind another preamble or
+// with other register numbers.  This cut gives k_gemm4 / k_gemm5 the instruction streams the
+// dispatch thresholds were measured with, instruction for instruction.
+typedef __attribute__((address_space(3))) void* lds_ptr;
+struct PpDesc {   // the f16 operands' buffer descriptors
+  __amdgpu_buffer_rsrc_t ra, rb;
+  __device__ __forceinline__ PpDesc(const ProjArgs& a, int bm) {
+    ra = __builtin_amdgcn_make_buffer_rsrc((void*)(a.A + (size_t)bm * G3_M * a.lda), (short)0,
+                                           max(0, a.M - bm * G3_M) * a.lda * 2, 0x00020000);
+    rb = __builtin_amdgcn_make_buffer_rsrc((void*)a.B, (short)0, a.N * a.ldb * 2, 0x00020000);
+  }
+};
+// the lane's loop-invariant DMA offsets (bytes): its row inside piece jj (of half h) and its swizzled chunk
+__device__ __forceinline__ uint32_t pp_chunk(int lane, int jj) { return (lane & 7) ^ ((4 * jj + (lane >> 4)) & 7); }
+__device__ __forceinline__ uint32_t pp_off_a(const ProjArgs& a, int wid, int lane, int h, int jj) {
+  const int p = 2 * wid + jj;
+  return (uint32_t)((p >> 3) * 128 + 64 * h + (p & 7) * 8 + (lane >> 3)) * (uint32_t)a.lda * 2u + pp_chunk(lane, jj) * 16u;
+}
+__device__ __forceinline__ uint32_t pp_off_b(const ProjArgs& a, int lane, int jj) {
+  return (uint32_t)(lane >> 3) * (uint32_t)a.ldb * 2u + pp_chunk(lane, jj) * 16u;
+}
+// row r of an image, k-step ks: the 16-B chunk 4 ks + fq of the row
+__device__ __forceinline__ f16x8 pp_frag(const f16* img, int r, int ks, int fq) {
+  return *(const f16x8*)(img + r * 64 + g2_swz(r, ks * 4 + fq) * 8);
+}
+struct PpFrags {
+  f16x8 af[2][4], bf[2][2];   // [ks][row tile], [ks][column tile] of the current quadrant
+  // quadrant (qa, qb): rows 64 qa.., column tiles 2 qb, 2 qb + 1 of the wave -- 16 MFMAs over the
+  // tile's 64 k, B fragment first (transposed accumulators)
+  template <int NJ>
+  __device__ void mfma(f32x4 (&acc)[8][NJ], int qa, int qb) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[qa * 4 + i][qb * 2 + j] =
+              __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[ks][j], af[ks][i], acc[qa * 4 + i][qb * 2 + j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+  }
+};
+
+// The two halves of a phase: {LDS fragment reads + LDS-DMA staging} pp_sync_in {MFMAs}
+// pp_sync_out.  sync_in: the fragments are in registers, then the barrier into the MFMA section.
+__device__ __forceinline__ void pp_sync_in() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void pp_sync_out() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Four-phase schedule of a 256 x 256 tile (k_gemm4, k_gemm8):
+//  * a K-tile is four phases, one output quadrant each -- Q(a, b) = the wave's rows 64a..64a+63 x
+//    columns 32b..32b+31 -- in the order Q00, Q01, Q11, Q10, so a phase reads 12, 4, 8 or 4
+//    fragments (A kept from Q00 to Q01, B1 from Q01 to Q11; B0 re-read for Q10);
+//  * waves 4-7 run one barrier behind waves 0-3: the two waves of every SIMD alternate, one
+//    multiplying while the other reads and stages (a ping-pong on the matrix pipe);
+//  * a half is restaged one phase after its last read: BH0 of tile t+1 in phase 1 of tile t, AH0 /
+//    BH1 / AH1 of tile t+2 in phases 2 / 3 / 4 (two LDS buffers, two tiles in flight);
+//  * one counted wait per tile (vmcnt(6): the three half-tiles staged after BH0 of tile t+1 stay
+//    in flight across the barriers), raw s_barrier (no __syncthreads fence that would drain them).
+template <int EPI>
+__device__ __forceinline__ void gemm_pp4_tile(const ProjArgs& a, f16* lds, int orig, int nwg) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bm, bn;
+  pp_tile_order<256>(a, orig, nwg, bm, bn);
+  const int grp = wid >> 2, wn = wid & 3;   // the wave's row group (128 rows) and column strip
+  constexpr int BK = G3_BK;
+  const PpDesc desc(a, bm);
+  uint32_t offa[2][2], offb[2];   // offa[half][jj]
 #pragma unroll
   for (int jj = 0; jj < 2; ++jj) {
-    const uint32_t ca = (lane & 7) ^ ((4 * jj + (lane >> 4)) & 7);
-    const int p = 2 * wid + jj;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-      offa[h][jj] = (uint32_t)((p >> 3) * 128 + 64 * h + (p & 7) * 8 + (lane >> 3)) * (uint32_t)a.lda * 2u + ca * 16u;
-    offb[jj] = (uint32_t)(lane >> 3) * (uint32_t)a.ldb * 2u + ca * 16u;
+    for (int h = 0; h < 2; ++h) offa[h][jj] = pp_off_a(a, wid, lane, h, jj);
+    offb[jj] = pp_off_b(a, lane, jj);
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   auto stage = [&](int buf, int half, int k0) {   // half: 0 AH0, 1 AH1, 2 BH0, 3 BH1
-    f16* dst = lds4 + (buf * 4 + half) * G4_HALF + (2 * wid) * 512;
+    f16* dst = lds + (buf * 4 + half) * G4_HALF + (2 * wid) * 512;
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int p = 2 * wid + jj;
       if (half < 2) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(dst + jj * 512), 16, offa[half][jj], k0 * 2, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(desc.ra, (lds_ptr)(dst + jj * 512), 16, offa[half][jj], k0 * 2, 0, 0);
       } else {
         const int row = bn * G3_N + (p >> 2) * 64 + 32 * (half - 2) + (p & 3) * 8;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr)(dst + jj * 512), 16, offb[jj], (row * a.ldb + k0) * 2, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(desc.rb, (lds_ptr)(dst + jj * 512), 16, offb[jj], (row * a.ldb + k0) * 2, 0, 0);
       }
     }
   };
-  const int nk = a.K / G3_BK;
+  const int nk = a.K / BK;
   // prologue: tile 0 and the halves of tile 1 staged ahead of the loop (AH0, BH1, AH1)
   stage(0, 0, 0);
   stage(0, 2, 0);
   stage(0, 3, 0);
   stage(0, 1, 0);
   if (nk > 1) {
-    stage(1, 0, G3_BK);
-    stage(1, 3, G3_BK);
-    stage(1, 1, G3_BK);
+    stage(1, 0, BK);
+    stage(1, 3, BK);
+    stage(1, 1, BK);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -502,15 +477,14 @@ __device__ __forceinline__ void gemm4_tile(const ProjArgs& a, f16* lds4, int ori
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int fr = lane & 15, fq = lane >> 4;
-  f16x8 af[2][4], bf[2][2];   // [ks][row tile], [ks][column tile] of the current quadrant
+  const int fr = lane & 15, fq = lane >> 4;   // the lane's row and k quarter in a 16-row MFMA fragment
+  PpFrags fg;
   auto read_a = [&](const f16* img) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int r = grp * 64 + i * 16 + fr;
-        af[ks][i] = *(const f16x8*)(img + r * 64 + g2_swz(r, ks * 4 + fq) * 8);
+        fg.af[ks][i] = pp_frag(img, grp * 64 + i * 16 + fr, ks, fq);
       }
   };
   auto read_b = [&](const f16* img) {
@@ -518,72 +492,47 @@ __device__ __forceinline__ void gemm4_tile(const ProjArgs& a, f16* lds4, int ori
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int r = wn * 32 + j * 16 + fr;
-        bf[ks][j] = *(const f16x8*)(img + r * 64 + g2_swz(r, ks * 4 + fq) * 8);
+        fg.bf[ks][j] = pp_frag(img, wn * 32 + j * 16 + fr, ks, fq);
       }
   };
-  auto mfma_q = [&](int qa, int qb) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[qa * 4 + i][qb * 2 + j] =
-              __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[ks][j], af[ks][i], acc[qa * 4 + i][qb * 2 + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // end of a load section: fragments in registers, then the barrier into the MFMA section
-  auto sync_in = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto sync_out = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  auto mfma = [&](int qa, int qb) { fg.mfma(acc, qa, qb); };
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    const f16* img = lds4 + cur * 4 * G4_HALF;
+    const f16* img = lds + cur * 4 * G4_HALF;   // + h * G4_HALF: AH[h]; + (2 + h) * G4_HALF: BH[h] / BT
     const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
-    // phase 1: Q00 -- read AH0 + BH0; stage BH0 of tile kt+1
+    // phase 1: Q00 -- read AH0 + BH0 ; stage BH0 of tile kt+1
     read_b(img + 2 * G4_HALF);
     read_a(img);
-    if (n1) stage(cur ^ 1, 2, (kt + 1) * G3_BK);
-    sync_in();
-    mfma_q(0, 0);
-    sync_out();
+    if (n1) stage(cur ^ 1, 2, (kt + 1) * BK);
+    pp_sync_in();
+    mfma(0, 0);
+    pp_sync_out();
     // phase 2: Q01 -- read BH1; stage AH0 of tile kt+2
     read_b(img + 3 * G4_HALF);
-    if (n2) stage(cur, 0, (kt + 2) * G3_BK);
-    sync_in();
-    mfma_q(0, 1);
-    sync_out();
+    if (n2) stage(cur, 0, (kt + 2) * BK);
+    pp_sync_in();
+    mfma(0, 1);
+    pp_sync_out();
     // phase 3: Q11 -- read AH1; stage BH1 of tile kt+2
     read_a(img + G4_HALF);
-    if (n2) stage(cur, 3, (kt + 2) * G3_BK);
-    sync_in();
-    mfma_q(1, 1);
-    sync_out();
+    if (n2) stage(cur, 3, (kt + 2) * BK);
+    pp_sync_in();
+    mfma(1, 1);
+    pp_sync_out();
     // phase 4: Q10 -- read BH0; stage AH1 of tile kt+2; retire everything up to BH0 of tile kt+1
     read_b(img + 2 * G4_HALF);
     if (n2) {
-      stage(cur, 1, (kt + 2) * G3_BK);
+      stage(cur, 1, (kt + 2) * BK);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
-    mfma_q(1, 0);
-    sync_out();
+    pp_sync_in();
+    mfma(1, 0);
+    pp_sync_out();
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();   // matches the stagger barrier of waves 4-7
-
   // transposed accumulators (B fragment first): lane (fr, fq) holds row fr, columns fq*4..+3 of
   // every 16 x 16 tile -- four consecutive columns, one vector access
   const bool hb = a.bias != nullptr;
@@ -598,88 +547,49 @@ __device__ __forceinline__ void gemm4_tile(const ProjArgs& a, f16* lds4, int ori
       epi_store4<EPI>(a, bm * G3_M + grp * 128 + i * 16 + fr, bn * G3_N + wn * 64 + j * 16 + fq * 4, acc[i][j], hb, bz[j]);
 }
 
-// Persistent form: gridDim.x workgroups (a multiple of 8, <= the tile count) walk the tiles
-// blockIdx.x, blockIdx.x + gridDim.x, ... -- every tile of a workgroup keeps its XCD, so the
-// XCD-grouped order holds.  Fewer workgroups than CUs leave CUs to the decode-step kernels that
-// run beside the encoder (WDR_GEMM_CUS).
+// Two-phase schedule of a 256 x 128 tile (k_gemm5, k_gemm8n) for the narrow encoder projections
+// (o, fc2: N = d = 1280), which fill only 120 of 256 CUs with 256 x 256 tiles at M = 6000 (240
+// with these): the four-phase schedule's stagger and barriers, a K-tile as two phases, one per
+// 64-row half of the wave's rows; the B fragments are read in phase 1 and kept for phase 2.  A
+// half is restaged one phase after its last read -- AH1 of tile t+1 in phase 1 of tile t, AH0 and
+// BT of tile t+2 in phase 2 -- and every phase ends its load section with a
+// counted wait (vmcnt(6): three half-tiles in flight across the barriers).
 template <int EPI>
-__global__ __launch_bounds__(512, 1) void k_gemm4(ProjArgs a) {
-  ProfClock prof_clock_(a.ts);   // sampled launches only (csrc/prof.cpp)
-  extern __shared__ __attribute__((aligned(16))) f16 lds4[];   // [buf][AH0, AH1, BH0, BH1][128 x 64]
-  const int ntiles = (a.N / G3_N) * cdiv(a.M, G3_M);
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    gemm4_tile<EPI>(a, lds4, t, ntiles);
-    __builtin_amdgcn_s_barrier();   // every wave's last LDS reads done before the next prologue
-  }
-}
-
-
-// ---------------------------------------------------------------- MFMA GEMM, 256 x 128 ping-pong
-// k_gemm4's schedule on a 256 x 128 tile for the narrow encoder projections (o, fc2: N = d =
-// 1280), which fill only 120 of 256 CUs with 256 x 256 tiles at M = 6000 (240 with these).
-// 8 waves, 2 along M x 4 along N, 128 x 32 outputs each; a K-tile (BK 64) is two phases, one per
-// 64-row half of the wave's rows (16 MFMAs each: 4 row x 2 column tiles x 2 k-steps); the B
-// fragments are read in phase 1 and kept for phase 2.  LDS per buffer: AH0 / AH1 (the two row
-// halves of both wave groups) and BT (the 128 B rows), 16 KB each, two buffers (96 KB); a half is
-// restaged one phase after its last read -- AH1 of tile t+1 in phase 1 of tile t, AH0 and BT of
-// tile t+2 in phase 2 -- and every phase ends its load section with a counted wait (vmcnt(6):
-// three half-tiles in flight across the barriers).  Same k order as k_gemm: bit-identical.
-constexpr uint32_t G5_LDS = 2u * 3u * G4_HALF * 2u;   // 96 KB
-
-template <int EPI>
-__device__ __forceinline__ void gemm5_tile(const ProjArgs& a, f16* lds5, int orig, int nwg) {
+__device__ __forceinline__ void gemm_pp2_tile(const ProjArgs& a, f16* lds, int orig, int nwg) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
-  const int ntn = a.N / 128;
-  int bm = id / ntn, bn = id % ntn;
-  if (a.tile_gm > 1) {
-    const int ntm = cdiv(a.M, G3_M), gsz = a.tile_gm * ntn, g = id / gsz, m0 = g * a.tile_gm;
-    const int gm = min(a.tile_gm, ntm - m0), l = id - g * gsz;
-    bm = m0 + l % gm;
-    bn = l / gm;
-  }
-  const int grp = wid >> 2, wn = wid & 3;
-  // staging: wave w writes pieces 2w, 2w+1 (8 image rows each) of every half
-  //   AH[h] image row q -> A row bm*256 + (q >> 6)*128 + 64h + (q & 63);  BT row q -> B row bn*128 + q
-  // buffer-resource DMA with loop-invariant lane offsets, as k_gemm4
-  // A: the descriptor starts at the tile's first row and ends at row M (rows past it read zeros:
-  // the buffer range check covers the VGPR offset, which carries the row), k0 in the scalar offset
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.A + (size_t)bm * G3_M * a.lda), (short)0, max(0, a.M - bm * G3_M) * a.lda * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)a.B, (short)0, a.N * a.ldb * 2, 0x00020000);
-  uint32_t offa[2][2], offb[2];   // offa[half][jj]: the row inside the tile and the chunk
+  int bm, bn;
+  pp_tile_order<128>(a, orig, nwg, bm, bn);
+  const int grp = wid >> 2, wn = wid & 3;   // the wave's row group (128 rows) and column strip
+  constexpr int BK = G3_BK;
+  const PpDesc desc(a, bm);
+  uint32_t offa[2][2], offb[2];   // offa[half][jj]
 #pragma unroll
   for (int jj = 0; jj < 2; ++jj) {
-    const uint32_t ca = (lane & 7) ^ ((4 * jj + (lane >> 4)) & 7);
-    const int p = 2 * wid + jj;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-      offa[h][jj] = (uint32_t)((p >> 3) * 128 + 64 * h + (p & 7) * 8 + (lane >> 3)) * (uint32_t)a.lda * 2u + ca * 16u;
-    offb[jj] = (uint32_t)(lane >> 3) * (uint32_t)a.ldb * 2u + ca * 16u;
+    for (int h = 0; h < 2; ++h) offa[h][jj] = pp_off_a(a, wid, lane, h, jj);
+    offb[jj] = pp_off_b(a, lane, jj);
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   auto stage = [&](int buf, int half, int k0) {   // half: 0 AH0, 1 AH1, 2 BT
-    f16* dst = lds5 + (buf * 3 + half) * G4_HALF + (2 * wid) * 512;
+    f16* dst = lds + (buf * 3 + half) * G4_HALF + (2 * wid) * 512;
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int p = 2 * wid + jj;
       if (half < 2) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(dst + jj * 512), 16, offa[half][jj], k0 * 2, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(desc.ra, (lds_ptr)(dst + jj * 512), 16, offa[half][jj], k0 * 2, 0, 0);
       } else {
         const int row = bn * 128 + p * 8;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr)(dst + jj * 512), 16, offb[jj], (row * a.ldb + k0) * 2, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(desc.rb, (lds_ptr)(dst + jj * 512), 16, offb[jj], (row * a.ldb + k0) * 2, 0, 0);
       }
     }
   };
-  const int nk = a.K / G3_BK;
+  const int nk = a.K / BK;
   stage(0, 0, 0);
   stage(0, 2, 0);
   stage(0, 1, 0);
   if (nk > 1) {
-    stage(1, 0, G3_BK);
-    stage(1, 2, G3_BK);
+    stage(1, 0, BK);
+    stage(1, 2, BK);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -694,15 +604,14 @@ __device__ __forceinline__ void gemm5_tile(const ProjArgs& a, f16* lds5, int ori
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int fr = lane & 15, fq = lane >> 4;
-  f16x8 af[2][4], bf[2][2];
+  const int fr = lane & 15, fq = lane >> 4;   // the lane's row and k quarter in a 16-row MFMA fragment
+  PpFrags fg;
   auto read_a = [&](const f16* img) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int r = grp * 64 + i * 16 + fr;
-        af[ks][i] = *(const f16x8*)(img + r * 64 + g2_swz(r, ks * 4 + fq) * 8);
+        fg.af[ks][i] = pp_frag(img, grp * 64 + i * 16 + fr, ks, fq);
       }
   };
   auto read_b = [&](const f16* img) {
@@ -710,68 +619,47 @@ __device__ __forceinline__ void gemm5_tile(const ProjArgs& a, f16* lds5, int ori
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int r = wn * 32 + j * 16 + fr;
-        bf[ks][j] = *(const f16x8*)(img + r * 64 + g2_swz(r, ks * 4 + fq) * 8);
+        fg.bf[ks][j] = pp_frag(img, wn * 32 + j * 16 + fr, ks, fq);
       }
   };
-  auto mfma_h = [&](int qa) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[qa * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[ks][j], af[ks][i], acc[qa * 4 + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto sync_in = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto sync_out = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  auto mfma = [&](int qa, int qb) { fg.mfma(acc, qa, qb); };
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    const f16* img = lds5 + cur * 3 * G4_HALF;
+    const f16* img = lds + cur * 3 * G4_HALF;   // + h * G4_HALF: AH[h]; + (2 + h) * G4_HALF: BH[h] / BT
     const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
-    // phase 1: rows 0..63 of the wave's half -- read AH0 + BT; stage AH1 of tile kt+1; retire AH1
-    // of tile kt (read in phase 2)
+    // phase 1: rows 0..63 of the wave's half -- read BT + AH0; stage AH1 of tile kt+1;
+    // retire AH1 of tile kt (read in phase 2)
     read_b(img + 2 * G4_HALF);
     read_a(img);
     if (n1) {
-      stage(cur ^ 1, 1, (kt + 1) * G3_BK);
+      stage(cur ^ 1, 1, (kt + 1) * BK);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
-    mfma_h(0);
-    sync_out();
-    // phase 2: rows 64..127 -- read AH1; stage AH0 + BT of tile kt+2; retire AH0 / BT of tile kt+1
+    pp_sync_in();
+    mfma(0, 0);
+    pp_sync_out();
+    // phase 2: rows 64..127 -- read AH1; stage AH0 and BT of tile kt+2; retire AH0 / BT of
+    // tile kt+1
     read_a(img + G4_HALF);
     if (n2) {
-      stage(cur, 0, (kt + 2) * G3_BK);
-      stage(cur, 2, (kt + 2) * G3_BK);
+      stage(cur, 0, (kt + 2) * BK);
+      stage(cur, 2, (kt + 2) * BK);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else if (n1) {
       asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
-    mfma_h(1);
-    sync_out();
+    pp_sync_in();
+    mfma(1, 0);
+    pp_sync_out();
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();   // matches the stagger barrier of waves 4-7
-
-  // transposed accumulators, as k_gemm4
+  // transposed accumulators (B fragment first): lane (fr, fq) holds row fr, columns fq*4..+3 of
+  // every 16 x 16 tile -- four consecutive columns, one vector access
   const bool hb = a.bias != nullptr;
   f32x4 bz[2];
 #pragma unroll
@@ -784,18 +672,30 @@ __device__ __forceinline__ void gemm5_tile(const ProjArgs& a, f16* lds5, int ori
       epi_store4<EPI>(a, bm * G3_M + grp * 128 + i * 16 + fr, bn * 128 + wn * 32 + j * 16 + fq * 4, acc[i][j], hb, bz[j]);
 }
 
+// Persistent form: gridDim.x workgroups (a multiple of 8, <= the tile count) walk the tiles
+// blockIdx.x, blockIdx.x + gridDim.x, ... -- every tile of a workgroup keeps its XCD, so the
+// XCD-grouped order holds.  Fewer workgroups than CUs leave CUs to the decode-step kernels that
+// run beside the encoder (WDR_GEMM_CUS).
 template <int EPI>
-__global__ __launch_bounds__(512, 1) void k_gemm5(ProjArgs a) {
+__global__ __launch_bounds__(512, 1) void k_gemm4(ProjArgs a) {
   ProfClock prof_clock_(a.ts);   // sampled launches only (csrc/prof.cpp)
-  extern __shared__ __attribute__((aligned(16))) f16 lds5[];   // [buf][AH0, AH1, BT][128 x 64]
-  const int ntiles = (a.N / 128) * cdiv(a.M, G3_M);
+  extern __shared__ __attribute__((aligned(16))) f16 lds4[];   // [buf][AH0, AH1, BH0, BH1][128 x 64]
+  const int ntiles = (a.N / G3_N) * cdiv(a.M, G3_M);
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    gemm5_tile<EPI>(a, lds5, t, ntiles);
+    gemm_pp4_tile<EPI>(a, lds4, t, ntiles);
     __builtin_amdgcn_s_barrier();   // every wave's last LDS reads done before the next prologue
   }
 }
-
-
+template <int EPI>
+__global__ __launch_bounds__(512, 1) void k_gemm5(ProjArgs a) {
+  ProfClock prof_clock_(a.ts);
+  extern __shared__ __attribute__((aligned(16))) f16 lds5[];   // [buf][AH0, AH1, BT][128 x 64]
+  const int ntiles = (a.N / 128) * cdiv(a.M, G3_M);
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    gemm_pp2_tile<EPI>(a, lds5, t, ntiles);
+    __builtin_amdgcn_s_barrier();   // every wave's last LDS reads done before the next prologue
+  }
+}
 // ---------------------------------------------------------------- fp8 (e4m3) MX MFMA GEMM
 // The encoder GEMMs of BASELINE configs[4] on the block-scaled fp8 MFMA
 // (v_mfma_scale_f32_16x16x128_f8f6f4: twice the f16 MFMA rate, MI355X_MICROARCH.md "Matrix
@@ -809,21 +709,17 @@ __global__ __launch_bounds__(512, 1) void k_gemm5(ProjArgs a) {
 // k = 128 kt + 32 b .. +32 of row r, so one K-tile's scales of a 256-row tile are one 1-KB run --
 // one LDS-DMA wave instruction.
 //
-// k_gemm8 is k_gemm4's ping-pong schedule byte for byte: a BK = 128 fp8 K-tile is the 128-B row
-// of k_gemm4's BK = 64 f16 tile, so the half-tile images, the g2_swz source swizzle, the four
-// quadrant phases, the stagger of waves 4-7 and the counted vmcnt(6) are unchanged; a quadrant is
-// 8 scaled MFMAs (4 row x 2 column tiles, K = 128: 32 cycles each -- the 256 cycles of k_gemm4's
-// 16 f16 MFMAs for twice the k).  A K-tile's two scale images are staged with its first half (BH0,
-// phase 1 of the tile before; waves 0 / 1, one DMA each) into a 4-KB double buffer behind the
-// tile images, retired by the same vmcnt(6), and read into registers in phase 1 of the tile.
-// Lane (fr, fq) of a 16 x 16 x 128 operand holds k = 16 fq .. +15 and 64 + 16 fq .. +15 of row fr
-// (bytes 0-15 / 16-31) and its scale register scales k-block fq (k = 32 fq .. +31), so the
-// fragment is the row's 16-B chunks fq and 4 + fq (test_mfma_scale_lane_map pins both maps).
+// k_gemm8 / k_gemm8n are the ping-pong schedules of k_gemm4 / k_gemm5 (gemm_pp4_tile /
+// gemm_pp2_tile above: the same images, staging, phases, stagger of waves 4-7 and counted waits)
+// written out for these operands: a BK = 128 fp8 K-tile is the 128-B row of the BK = 64 f16 tile;
+// a quadrant is 8 scaled MFMAs (4 row x 2 column tiles, K = 128: 32 cycles each -- the 256 cycles
+// of the 16 f16 MFMAs for twice the k).  k_gemm8n: the narrow projections (o, fc2: N = d = 1280),
+// 240 tiles at M = 6000 where k_gemm8's 256 x 256 tiles leave half the CUs idle.  They are not
+// instances of the f16 schedule templates: built from shared templates with an operand policy the
+// fp8 kernels kept their K loop, register counts and waits but measured 1-2 % slower at the
+// large-v3 shapes (profiles/r08/gemm_bench_refactor.txt).
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int G8_BK = 128;                              // k per K-tile (bytes per row)
-constexpr uint32_t G8_SC = 2u * 2u * 1024u;             // scale images: [buf][A | B][256 words]
-constexpr uint32_t G8_LDS = G4_LDS + G8_SC;             // 132 KB
 
 // E8M0 exponent of an F8 block whose largest magnitude is amax: the smallest e with
 // amax / 2^e <= 448 (e4m3's largest finite value), exactly -- amax = m 2^x, m in [0.5, 1), and
@@ -863,28 +759,10 @@ template <int EPI>
 __device__ __forceinline__ void gemm8_tile(const ProjArgs& a, uint8_t* lds, int orig, int nwg) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
-  const int ntn = a.N / G3_N;
-  int bm = id / ntn, bn = id % ntn;
-  if (a.tile_gm > 1) {
-    const int ntm = cdiv(a.M, G3_M), gsz = a.tile_gm * ntn, g = id / gsz, m0 = g * a.tile_gm;
-    const int gm = min(a.tile_gm, ntm - m0), l = id - g * gsz;
-    bm = m0 + l % gm;
-    bn = l / gm;
-  }
+  int bm, bn;
+  pp_tile_order<256>(a, orig, nwg, bm, bn);
   const int grp = wid >> 2, wn = wid & 3;
-  // staging as k_gemm4 (bytes): AH[h] image row q -> A row bm*256 + (q >> 6)*128 + 64h + (q & 63),
-  // BH[h] image row q -> B row bn*256 + (q >> 5)*64 + 32h + (q & 31), q = (2 wid + jj)*8 + lane/8.
-  // Buffer-resource DMA (buffer_load_dwordx4 ... lds): the row base and k0 are a wave-uniform
-  // scalar offset, a lane adds one loop-invariant 32-bit offset per piece jj -- its row lane/8 and
-  // its g2_swz chunk ((lane & 7) ^ ((4 jj + lane/16) & 7): wid drops out).  A VGPR that an LDS
-  // DMA reads is then never rewritten: hipcc treats an LDS-DMA's VGPR operands like store data and
-  // puts an s_waitcnt vmcnt(0) in front of any redefinition, which with per-K-tile 64-bit
-  // addresses sat at the head of every K-tile and drained the two tiles in flight.  Rows past M
-  // read zeros (the descriptor's bounds), and are never stored.
-  // A: the descriptor starts at the tile's first row and ends at row M (rows past it read zeros:
-  // the buffer range check covers the VGPR offset, which carries the row), k0 in the scalar offset
+  // staging as gemm_pp4_tile, in bytes ("Staging of the half-tile images" above)
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(a.A8 + (size_t)bm * G3_M * a.lda), (short)0, max(0, a.M - bm * G3_M) * a.lda, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)a.B8, (short)0, a.N * a.ldb, 0x00020000);
@@ -992,17 +870,6 @@ __device__ __forceinline__ void gemm8_tile(const ProjArgs& a, uint8_t* lds, int 
       asm volatile("" : "+v"(acc[qa * 4 + i][qb * 2]), "+v"(acc[qa * 4 + i][qb * 2 + 1]));
     __builtin_amdgcn_s_setprio(0);
   };
-  auto sync_in = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto sync_out = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
@@ -1017,23 +884,23 @@ __device__ __forceinline__ void gemm8_tile(const ProjArgs& a, uint8_t* lds, int 
       stage_sc(cur ^ 1, kt + 1);
       stage(cur ^ 1, 2, (kt + 1) * G8_BK);
     }
-    sync_in();
+    pp_sync_in();
     mfma_q(0, 0);
-    sync_out();
+    pp_sync_out();
     // phase 2: Q01 -- read BH1; stage AH0 of tile kt+2
     read_sc(cur, 0, 1);
     read_b(img + 3 * HB);
     if (n2) stage(cur, 0, (kt + 2) * G8_BK);
-    sync_in();
+    pp_sync_in();
     mfma_q(0, 1);
-    sync_out();
+    pp_sync_out();
     // phase 3: Q11 -- read AH1; stage BH1 of tile kt+2
     read_sc(cur, 1, 1);
     read_a(img + HB);
     if (n2) stage(cur, 3, (kt + 2) * G8_BK);
-    sync_in();
+    pp_sync_in();
     mfma_q(1, 1);
-    sync_out();
+    pp_sync_out();
     // phase 4: Q10 -- read BH0; stage AH1 of tile kt+2; retire everything up to BH0 (and the
     // scales) of tile kt+1
     read_sc(cur, 1, 0);
@@ -1044,9 +911,9 @@ __device__ __forceinline__ void gemm8_tile(const ProjArgs& a, uint8_t* lds, int 
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
+    pp_sync_in();
     mfma_q(1, 0);
-    sync_out();
+    pp_sync_out();
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();   // matches the stagger barrier of waves 4-7
 
@@ -1119,25 +986,16 @@ __global__ __launch_bounds__(512, 1) void k_gemm8(ProjArgs a) {
 // (256 rows) and B (128 rows, the first 512 B of the image) per K-tile, in a 3-deep ring: a
 // K-tile's scales are staged with its AH0 / BT (phase 2 of the tile two before), so the tile in
 // between still reads its own.
-constexpr uint32_t G8N_LDS = 2u * 3u * G4_HALF * 2u + 3u * 2048u;   // 96 KB + 6 KB
 
 template <int EPI>
 __device__ __forceinline__ void gemm8n_tile(const ProjArgs& a, uint8_t* lds, int orig, int nwg) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
-  const int ntn = a.N / 128;
-  int bm = id / ntn, bn = id % ntn;
-  if (a.tile_gm > 1) {
-    const int ntm = cdiv(a.M, G3_M), gsz = a.tile_gm * ntn, g = id / gsz, m0 = g * a.tile_gm;
-    const int gm = min(a.tile_gm, ntm - m0), l = id - g * gsz;
-    bm = m0 + l % gm;
-    bn = l / gm;
-  }
+  int bm, bn;
+  pp_tile_order<128>(a, orig, nwg, bm, bn);
   const int grp = wid >> 2, wn = wid & 3;
-  // staging (bytes) as k_gemm5: AH[h] image row q -> A row bm*256 + (q >> 6)*128 + 64h + (q & 63);
-  // BT row q -> B row bn*128 + q; buffer-resource DMA as k_gemm8 (rows past M read zeros)
+  // staging as gemm_pp2_tile, in bytes ("Staging of the half-tile images" above); BT's piece row
+  // rides in the lane offset here, not in the scalar one
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(a.A8 + (size_t)bm * G3_M * a.lda), (short)0, max(0, a.M - bm * G3_M) * a.lda, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)a.B8, (short)0, a.N * a.ldb, 0x00020000);
@@ -1231,17 +1089,6 @@ __device__ __forceinline__ void gemm8n_tile(const ProjArgs& a, uint8_t* lds, int
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(acc[h * 4 + i][0]), "+v"(acc[h * 4 + i][1]));
     __builtin_amdgcn_s_setprio(0);
   };
-  auto sync_in = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto sync_out = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
@@ -1258,9 +1105,9 @@ __device__ __forceinline__ void gemm8n_tile(const ProjArgs& a, uint8_t* lds, int
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
+    pp_sync_in();
     mfma_h(0);
-    sync_out();
+    pp_sync_out();
     // phase 2: rows 64..127 -- read AH1; stage the scales, AH0 and BT of tile kt+2; retire AH0 /
     // BT (and the scales) of tile kt+1
     read_a(img + HB, sc, 1);
@@ -1274,9 +1121,9 @@ __device__ __forceinline__ void gemm8n_tile(const ProjArgs& a, uint8_t* lds, int
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sync_in();
+    pp_sync_in();
     mfma_h(1);
-    sync_out();
+    pp_sync_out();
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();   // matches the stagger barrier of waves 4-7
 
@@ -1303,38 +1150,36 @@ __global__ __launch_bounds__(512, 1) void k_gemm8n(ProjArgs a) {
   }
 }
 
+// Launch what the dispatch rule (csrc/gemm_plan.cpp) planned; the kernel's dynamic-LDS limit is
+// raised once per instantiation (a kernel's plans all carry the same LDS size).
+template <auto KERNEL>
+static void launch_planned(const GemmPlan& p, int threads, double bytes, double flops, const ProjArgs& a, hipStream_t s) {
+  static const bool attr = [&] {
+    if (p.lds)
+      WDR_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    return true;
+  }();
+  (void)attr;
+  wdr_launch(PROF_GEMM, bytes, flops, KERNEL, dim3(p.grid_x, p.grid_y), dim3(threads), p.lds, s, a);
+}
+static GemmShape plan_shape(const ProjArgs& a, bool fp8) {
+  return {a.M, a.N, a.K, a.epi, a.ldo, a.d, a.gemm_ref != 0, fp8};
+}
+
 template <int EPI>
 static void launch_epi8(const ProjArgs& a, hipStream_t s) {
   // algorithmic bytes: fp8 operands + their scales, the output at its epilogue's width
   const double ob = EPI == EPI_F8_GELU ? 1.0 : (EPI == EPI_F32_RESID || EPI == EPI_F32) ? 4.0 : 2.0;
   const double bytes = ((double)a.N + a.M) * a.K * (1.0 + 1.0 / 32) + (double)a.M * a.N * ob;
   const double flops = 2.0 * a.M * a.N * a.K;
-  static bool attr = [] {
-    WDR_HIP(hipFuncSetAttribute((const void*)k_gemm8<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G8_LDS));
-    return true;
-  }();
-  (void)attr;
-  static const int tile_gm = getenv("WDR_GEMM4_GM") ? atoi(getenv("WDR_GEMM4_GM")) : 4;   // as k_gemm4
+  const GemmKnobs& kn = gemm_knobs();
+  const GemmPlan p = gemm_plan(plan_shape(a, true), kn);
   ProjArgs g = a;
-  g.tile_gm = tile_gm;
+  g.tile_gm = kn.tile_gm;
   if constexpr (EPI != EPI_F8_GELU) {
-    // the narrow projections (o, fc2: N = 1280) on 256 x 128 tiles: 240 at M = 6000 where 256 x 256
-    // tiles fill 120 CUs (WDR_GEMM8N=0: k_gemm8 for every shape)
-    // N % 256 != 0 (tiny's qkv, N = 1152) has only the 256 x 128 tiling
-    static const bool narrow_on = !getenv("WDR_GEMM8N") || atoi(getenv("WDR_GEMM8N")) != 0;
-    if ((narrow_on && a.N < 2048) || a.N % G3_N != 0) {
-      static bool attrn = [] {
-        WDR_HIP(hipFuncSetAttribute((const void*)k_gemm8n<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G8N_LDS));
-        return true;
-      }();
-      (void)attrn;
-      const int ntn = (a.N / 128) * cdiv(a.M, G3_M);
-      wdr_launch(PROF_GEMM, bytes, flops, k_gemm8n<EPI>, dim3(ntn), dim3(512), G8N_LDS, s, g);
-      return;
-    }
+    if (p.kernel == K_GEMM8N) return launch_planned<k_gemm8n<EPI>>(p, 512, bytes, flops, g, s);
   }
-  const int ntiles = (a.N / G3_N) * cdiv(a.M, G3_M);
-  wdr_launch(PROF_GEMM, bytes, flops, k_gemm8<EPI>, dim3(ntiles), dim3(512), G8_LDS, s, g);
+  launch_planned<k_gemm8<EPI>>(p, 512, bytes, flops, g, s);
 }
 
 void launch_proj_fp8(const ProjArgs& a, hipStream_t s) {
@@ -1646,113 +1491,21 @@ __global__ __launch_bounds__(W * 64) void k_skinny(ProjArgs a) {
 }
 
 
-
-// A/B knobs of the encoder GEMM dispatch, read once per process (gemm_knobs_reload: tools/gemm_bench
-// A/B runs set them per variant): WDR_GEMM1=1 every M > 64 projection on k_gemm; WDR_GEMM3=0 the
-// big shapes off k_gemm3; WDR_GEMM4=0|1 the ping-pong 256 x 256 GEMM off / forced on for every
-// shape it takes (unset: the measured dispatch rule); WDR_GEMM4_GM row tiles per group of the
-// k_gemm4 / k_gemm5 tile order (default 4); WDR_GEMM5=1 the narrow projections on k_gemm5's
-// 256 x 128 tiles; WDR_GEMM_CUS persistent k_gemm4 / k_gemm5 workgroups (multiple of 8; default one per
-// tile)
-struct GemmKnobs {
-  bool gemm1, gemm3, gemm5, gemm5w;
-  int gemm4, tile_gm, cus;
-};
-static int env_int(const char* name, int def) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : def;
-}
-static GemmKnobs read_knobs() {
-  GemmKnobs k;
-  k.gemm1 = env_int("WDR_GEMM1", 0) != 0;
-  k.gemm3 = env_int("WDR_GEMM3", 1) != 0 && !k.gemm1;
-  k.gemm4 = env_int("WDR_GEMM4", -1);
-  k.tile_gm = env_int("WDR_GEMM4_GM", 4);
-  // k_gemm5 off by default since round 4: on the encode-ahead streams' 224 CUs its 240 tiles of
-  // o / fc2 take two rounds where k_gemm4's 120 take one and leave ~100 CUs to the decode chain
-  // (1-h bench 737-739 vs 725-731 xRT, profiles/r04/ab_gemm5.txt)
-  k.gemm5 = env_int("WDR_GEMM5", 0) != 0;
-  k.gemm5w = env_int("WDR_GEMM5_WIDE", 1) != 0;
-  k.cus = env_int("WDR_GEMM_CUS", 0) / 8 * 8;
-  return k;
-}
-static GemmKnobs& knobs() {
-  static GemmKnobs k = read_knobs();
-  return k;
-}
-void gemm_knobs_reload() { knobs() = read_knobs(); }
-
 template <int EPI>
 static void launch_epi(const ProjArgs& a, hipStream_t s) {
   const int ob = (EPI == EPI_F32_RESID || EPI == EPI_F32 || EPI == EPI_F32_GELU_POS) ? 4 : 2;
   const double bytes = (double)a.N * a.K * 2 + (double)a.M * a.K * 2 + (double)a.M * a.N * ob;
   const double flops = 2.0 * a.M * a.N * a.K;
   WDR_CHECK(a.M > 64, "encoder GEMM: more than 64 rows (fewer go to the row kernel)");
-  const GemmKnobs& kn = knobs();
-  const bool ref = kn.gemm1 || a.gemm_ref;
-  const bool vec4 = a.ldo % 4 == 0 && (a.epi != EPI_QKV_CACHE || a.d % 4 == 0);   // epi_store4
-  // fc1 (N = 4d) on k_gemm5's 256 x 128 tiles (WDR_GEMM5_WIDE, default on): on the encode-ahead
-  // streams' 224 CUs k_gemm4's 480 tiles take 3 rounds where k_gemm5's 960 half-size tiles take
-  // 5 (2.5 of the big ones); alone both run at the same per-tile rate (875 TFLOP/s)
-  const bool wide5 = kn.gemm5w && a.N >= 4096 && a.N < 16384 && a.M >= 4096;
-  if (a.N % 128 == 0 && a.K % G3_BK == 0 && a.M >= 4096 && !ref && vec4 && kn.gemm4 != 0 &&
-      (wide5 || (a.N < 2048 && kn.gemm5 && (a.N / G3_N) * cdiv(a.M, G3_M) < 192))) {
-    // the narrow encoder projections (o, fc2) where 256 x 256 tiles would leave CUs idle: 256 x
-    // 128 tiles fill 240 of 256 CUs at M = 6000 (tools/gemm_bench: o 53 vs 62 us on k_gemm2, fc2
-    // 107 vs 126 us; at M = 12000 k_gemm4's 235 tiles are faster: fc2 194 vs 216 us)
-    static bool attr5 = [] {
-      WDR_HIP(hipFuncSetAttribute((const void*)k_gemm5<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G5_LDS));
-      return true;
-    }();
-    (void)attr5;
-    ProjArgs g = a;
-    g.tile_gm = kn.tile_gm;
-    const int ntiles5 = (a.N / 128) * cdiv(a.M, G3_M);
-    dim3 grid(kn.cus > 0 && kn.cus < ntiles5 ? kn.cus : ntiles5);
-    wdr_launch(PROF_GEMM, bytes, flops, k_gemm5<EPI>, grid, dim3(512), G5_LDS, s, g);
-  } else if (a.N % G3_N == 0 && a.K % G3_BK == 0 && !ref && vec4 &&
-             (kn.gemm4 == 1 ||
-              (kn.gemm4 != 0 && (a.M >= 4096 || a.N >= 16384 || (a.N >= 4096 && a.M > 1024) ||
-                                 (a.N >= 3072 && a.M >= 2560))))) {
-    // round 6, partial encode batches and on-demand windows (profiles/r06/gemm_bench_mid_m.txt,
-    // bit-identical outputs): fc1 (N = 4d) at M = 1500 / 3000 39.7 / 44.4 us on k_gemm4 vs 45.0 /
-    // 67.3 on k_gemm / k_gemm3; qkv (3d) at M = 3000 41.9 vs 50.2 (k_gemm2), at M = 1500 29.2 on
-    // k_gemm2 stays; o / fc2 (N = d) below M = 4096 stay on k_gemm2 (25.7 / 68.5 vs 43.3 / 110.4)
-    // ping-pong 256 x 256 tiles (tools/gemm_bench, large-v3, alone on the GPU): M = 6000 qkv 600
-    // vs 557 (k_gemm2), fc1 616 vs 574 (k_gemm3), cross-K/V 818 vs 742 TFLOP/s; M = 12000 every
-    // shape (o 394 vs 382, fc2 811 vs 743); M = 1500 cross-K/V 773 vs 616.  The N = 1280 shapes
-    // at M = 6000 fill only 120 of 256 CUs (alone: 209 / 478 vs 314 / 618 TFLOP/s on k_gemm2),
-    // but inside the pipeline the CUs they leave run decode steps: 1-h bench 480 vs 476 xRT.
-    static bool attr4 = [] {
-      WDR_HIP(hipFuncSetAttribute((const void*)k_gemm4<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS));
-      return true;
-    }();
-    (void)attr4;
-    const int ntiles = (a.N / G3_N) * cdiv(a.M, G3_M);
-    dim3 grid(kn.cus > 0 && kn.cus < ntiles ? kn.cus : ntiles);
-    ProjArgs g = a;
-    g.tile_gm = kn.tile_gm;
-    wdr_launch(PROF_GEMM, bytes, flops, k_gemm4<EPI>, grid, dim3(512), G4_LDS, s, g);
-  } else if ((a.N >= 5120 || a.M >= 9000) && a.M > 2048 && a.N % G3_N == 0 && a.K % G3_BK == 0 && kn.gemm3 && !ref) {
-    // 256 x 256 tiles where they measured faster (tools/gemm_bench, large-v3 shapes): M = 6000
-    // fc1 574 vs 509 TFLOP/s, cross-K/V 743 vs 641; at M = 12000 every encoder shape (qkv 667 vs
-    // 520, o 387 vs 335, fc1 550 vs 527, fc2 746 vs 620).  Below that the 120..360 tiles of the
-    // N <= 3840 shapes leave CUs idle and k_gemm2's 128 x 128 tiles win.
-    static bool attr = [] {
-      WDR_HIP(hipFuncSetAttribute((const void*)k_gemm3<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G3_LDS));
-      return true;
-    }();
-    (void)attr;
-    dim3 grid((a.N / G3_N) * cdiv(a.M, G3_M));
-    wdr_launch(PROF_GEMM, bytes, flops, k_gemm3<EPI>, grid, dim3(512), G3_LDS, s, a);
-  } else if (a.K % G2_BK == 0 && a.N <= 4096 && !ref && vec4) {
-    // LDS-DMA GEMM where it measured faster (tools/gemm_bench, M = 6000: qkv -5 %, o -11 %,
-    // fc2 -23 %; fc1 and the 82k-column cross-K/V GEMM stay on k_gemm, +8 % / +7 % there)
-    dim3 grid((a.N / GB_N) * cdiv(a.M, GB_M));
-    wdr_launch(PROF_GEMM, bytes, flops, k_gemm2<EPI>, grid, dim3(256), 0, s, a);
-  } else {
-    dim3 grid(a.N / GB_N, cdiv(a.M, GB_M));
-    wdr_launch(PROF_GEMM, bytes, flops, k_gemm<EPI>, grid, dim3(256), 0, s, a);
+  const GemmKnobs& kn = gemm_knobs();
+  const GemmPlan p = gemm_plan(plan_shape(a, false), kn);
+  ProjArgs g = a;
+  if (p.kernel == K_GEMM4 || p.kernel == K_GEMM5) g.tile_gm = kn.tile_gm;
+  switch (p.kernel) {
+    case K_GEMM5: launch_planned<k_gemm5<EPI>>(p, 512, bytes, flops, g, s); break;
+    case K_GEMM4: launch_planned<k_gemm4<EPI>>(p, 512, bytes, flops, g, s); break;
+    case K_GEMM2: launch_planned<k_gemm2<EPI>>(p, 256, bytes, flops, g, s); break;
+    default: launch_planned<k_gemm<EPI>>(p, 256, bytes, flops, g, s); break;
   }
 }
 
@@ -1764,6 +1517,10 @@ static void launch_epi(const ProjArgs& a, hipStream_t s) {
 // for the residual projections, to share CUs with the encoder GEMM tiles: slower alone --
 // tools/rows_bench, o 15.0 vs 5.1 us, fc2 21.1 vs 13.7 us at 16 rows -- and 5 % slower in the
 // 1-h pipeline, profiles/r04/ab_epi4.txt.)
+static int env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
+}
 // WDR_ROWS_PAIR=0: narrow projections of more than 32 rows one row tile per workgroup (A/B; read
 // once)
 static bool rows_pair_tiles() {

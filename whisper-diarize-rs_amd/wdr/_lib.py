@@ -160,6 +160,7 @@ _SIGS = {
     "wdr_context_set_encoder_fp8": (C.c_int, [vp, C.c_int8]),
     "wdr_dbg_set_early_fixup": (C.c_int, [vp, i32]),
     "wdr_dbg_set_gemm32": (C.c_int, [i32]),
+    "wdr_dbg_gemm_plan": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, P(i32), P(i32)]),
     "wdr_ggml_info": (C.c_int, [cstr, P(i32), P(i64), P(i64)]),
     "wdr_ggml_tensor_types": (C.c_int, [cstr, P(i64)]),
     "wdr_ggml_tensor_f16": (C.c_int, [cstr, cstr, P(P(C.c_uint16)), P(sz)]),
