@@ -385,6 +385,28 @@ int wdr_dbg_set_gemm32(int32_t mfma);
  * bytes}.  Host arithmetic only: never touches the GPU. */
 int wdr_dbg_gemm_plan(int32_t fp8, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t ldo, int32_t d,
                       int32_t gemm_ref, const int32_t* knobs, int32_t* plan_out /* [4] */);
+/* test seams: stream placement (csrc/streams.h).  Host arithmetic only: neither touches the GPU.
+ * wdr_dbg_cu_mask: the CU mask of a stream that leaves n_res of ncu CUs free under reservation
+ * pattern pat (only_reserved: the complement), n_words = (ncu + 31) / 32 words; an impossible
+ * request fails with the message the stream's creation would throw.
+ * wdr_dbg_stream_plan: what stream a role (0 context, 1 step batcher, 2 DTW queue, 3 state's own,
+ * 4 state's encode-ahead, 5 state's on-demand encodes, 6 state's DTW) gets on a device of ncu CUs.
+ * knobs null: the process's environment; else int32[14] {WDR_ENC_POOL, WDR_ENC_MASK,
+ * WDR_ENC_MASK_PAT, WDR_ENC_PRIO, WDR_OWN_POOL, WDR_OWN_MASK, WDR_OWN_PRIO, WDR_ODM_POOL,
+ * WDR_ODM_MASK, WDR_BATCH_HWQ, WDR_DTWQ_HWQ, then whether WDR_ENC_POOL / WDR_ENC_MASK /
+ * WDR_ODM_POOL is set at all}. */
+typedef struct wdr_stream_plan {
+  int32_t kind;      /* 0 no stream, 1 priority stream, 2 CU-masked, 3 CU-masked over every CU */
+  int32_t prio;      /* kind 1: 0 lowest, 1 middle, 2 highest, 3 created without a priority */
+  int32_t pool;      /* kind 2: streams in the shared pool, 0 = a stream of its own */
+  int32_t n_words;   /* kinds 2, 3: mask words */
+  uint32_t mask[16];
+  char tag[32];      /* WDR_STREAM_LOG name at creation, "" = not logged there */
+} wdr_stream_plan;
+int wdr_dbg_cu_mask(int32_t ncu, int32_t n_res, int32_t pat, int32_t only_reserved, uint32_t* words_out,
+                    int32_t n_words);
+int wdr_dbg_stream_plan(int32_t role, int32_t ncu, const int32_t* knobs /* [14] or null */,
+                        wdr_stream_plan* plan_out);
 int wdr_context_stage_times(wdr_context* c, wdr_stage_times* out);
 int wdr_context_hparams(wdr_context* c, int32_t* out /* [10] */);
 

@@ -19,6 +19,34 @@ def test_library_exports_every_header_symbol(lib):
     assert lib.wdr_abi_version() == 6
 
 
+def test_knob_table_lists_what_the_code_reads():
+    """INTEGRATION.md §5 against csrc: every variable passed to an env.h helper has a row, every
+    row names a variable some code reads (WDR_AB_LIB: the Python binding), and env.h is the only
+    file under csrc that reads the environment."""
+    import glob
+    import re
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    read, direct = {"WDR_AB_LIB"}, []
+    srcs = [f for f in glob.glob(os.path.join(root, "whisper-diarize-rs_amd", "csrc", "**", "*"), recursive=True)
+            if os.path.isfile(f)]
+    assert len(srcs) > 30
+    for f in srcs:
+        txt = open(f, errors="replace").read()
+        read |= set(re.findall(r'\benv_(?:set|int|on|double|str)\(\s*"(WDR_[A-Z0-9_]+)"', txt))
+        if "getenv(" in txt and os.path.basename(f) != "env.h":
+            direct.append(os.path.relpath(f, root))
+    assert not direct, direct
+    doc = open(os.path.join(root, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 5. Environment knobs"):]
+    table = set()
+    for line in sec.splitlines():
+        if line.startswith("| `"):
+            table |= set(re.findall(r"`(WDR_[A-Z0-9_]+)", line.split("|")[1]))
+    assert len(read) > 60
+    assert read - table == set(), "read by the code, no row in INTEGRATION.md"
+    assert table - read == set(), "in INTEGRATION.md, read by no code"
+
+
 def _wav(path, samples, ch=1, rate=16000, bits=16, fmt=1):
     data = np.asarray(samples, np.int16).tobytes() if bits == 16 else bytes(len(samples))
     hdr = b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE"

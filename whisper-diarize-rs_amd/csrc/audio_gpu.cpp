@@ -223,7 +223,7 @@ std::vector<int16_t> AudioConverter::run(const Fill& fill, uint64_t n_frames, in
     throw;
   }
   last.total = now_s() - t_start;
-  if (const char* v = getenv("WDR_AUDIO_LOG"))
+  if (const char* v = env_str("WDR_AUDIO_LOG"))
     if (v[0] == '1')
       fprintf(stderr, "wdr audio: %llu frames in %lld chunks: total %.4f s = setup %.4f + fill %.4f + gpu wait %.4f + rest\n",
               (unsigned long long)n_frames, last.chunks, last.total, last.setup, last.fill, last.wait);

@@ -9,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "env.h"         // the environment knobs' one reader
 #include "gemm_plan.h"   // Epi, the encoder GEMM tile constants, knobs and dispatch rule
 
 namespace wdr {

@@ -39,6 +39,7 @@
 #include "ggml_file.h"
 #include "model_files.h"
 #include "prof.h"
+#include "streams.h"
 
 using namespace wdr;
 
@@ -507,7 +508,7 @@ static std::unique_ptr<wdr_context> make_context(const std::string& model_name, 
   // explicitly (two models on one GPU exercise the multi-GPU path on a one-GPU machine)
   if (has_dev) {
     c->devices = {dev};
-  } else if (const char* e = getenv("WDR_DEVICES")) {
+  } else if (const char* e = env_str("WDR_DEVICES")) {
     // validated here, not later as HIP errors: ordinals of visible GPUs, at most 8 entries
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n < 1) throw std::runtime_error("WDR_DEVICES: no visible GPU");
@@ -723,8 +724,8 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
   // with the skew the chains' ends show no trend in k)
   std::vector<size_t> cut(C + 1, 0);
   {
-    static const double seg_s = getenv("WDR_BALANCE_SEG_S") ? atof(getenv("WDR_BALANCE_SEG_S")) : 0.0;
-    static const double skew = getenv("WDR_BALANCE_SKEW") ? atof(getenv("WDR_BALANCE_SKEW")) : 0.08;
+    static const double seg_s = env_double("WDR_BALANCE_SEG_S", 0.0);
+    static const double skew = env_double("WDR_BALANCE_SKEW", 0.08);
     std::vector<double> P(N + 1, 0.0);
     for (size_t i = 0; i < N; ++i) P[i + 1] = P[i] + (double)segs[i].n_samples + seg_s * 16000.0;
     std::vector<double> F(C + 1, 0.0);   // cumulative share of chains 0 .. k-1
@@ -792,7 +793,7 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
       // the speculative pass detected this segment's language from its window 0 alone: the
       // re-decode keeps it instead of a detection pass of its own
       // (WDR_LANG_HINT=0: detect again, A/B)
-      static const bool hint_on = !(getenv("WDR_LANG_HINT") && atoi(getenv("WDR_LANG_HINT")) == 0);
+      static const bool hint_on = env_on("WDR_LANG_HINT", true);
       st.lang_hint = hint_on && out[j].lang_known ? out[j].lang_id : -1;
       if (st.full(with_prompt(params, e), x.data(), (int)x.size(), -1, false) != 0)
         throw std::runtime_error("failed to transcribe");
@@ -908,7 +909,7 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
     // redone blocks as small batches at the end.  If the predecessor's own early fix-up later
     // changes that prompt, the rounds redo this block again: exact either way.
     try {
-      static const int env_mode = getenv("WDR_EARLY_FIXUP") ? atoi(getenv("WDR_EARLY_FIXUP")) : 3;
+      static const int env_mode = env_int("WDR_EARLY_FIXUP", 3);
       const int mode = c->early_fixup >= 0 ? c->early_fixup : env_mode;
       if (mode == 2 && k > 0)
         while (!done[k - 1].load() && !stop) std::this_thread::sleep_for(std::chrono::microseconds(200));
@@ -1091,7 +1092,7 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
       c->cam_path = path;
     }
   }
-  static const bool lowq_at_pipe = !(getenv("WDR_LOWQ_AT_PIPE") && atoi(getenv("WDR_LOWQ_AT_PIPE")) == 0);
+  static const bool lowq_at_pipe = env_on("WDR_LOWQ_AT_PIPE", true);
   if (!diarize && !c->low_dummy && lowq_at_pipe) {
     // WDR_LOWQ_AT_PIPE (default 1): an un-diarized pipeline gets a lowest-priority stream where the
     // embedding model's would be (before the decode chains' states on the first call), its
@@ -1099,13 +1100,8 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
     // lowest-priority DTW streams over its 4 low queues; measured: configs[2]'s VAD line 632 ->
     // 737-740 xRT, the diarized line unaffected (it never takes this branch);
     // profiles/r06/ab_lines_hwq.txt, DESIGN.md §5 "Hardware queues, round 6"
-    int lo = 0, hi = 0;
     WDR_HIP(hipSetDevice(c->devices[0]));
-    WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    WDR_HIP(hipStreamCreateWithPriority(&c->low_dummy, hipStreamNonBlocking, lo));
-    DevMem one(16);
-    WDR_HIP(hipMemsetAsync(one.p, 0, 16, c->low_dummy));
-    WDR_HIP(hipStreamSynchronize(c->low_dummy));
+    c->low_dummy = prime_queue(StreamPrio::Lowest);
   }
   std::unique_ptr<EmbedAhead> embeds;
   if (diarize) embeds = std::make_unique<EmbedAhead>(*c->cam, segs);
@@ -1119,11 +1115,10 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
       for (auto& t : th) t.join();
     }
   } spin;
-  if (const char* e = getenv("WDR_HOST_SPIN"))
-    for (int i = 0; i < std::max(0, std::min(8, atoi(e))); ++i)
-      spin.th.emplace_back([&spin] {
-        while (!spin.stop.load(std::memory_order_relaxed)) __builtin_ia32_pause();
-      });
+  for (int i = 0; i < std::max(0, std::min(8, env_int("WDR_HOST_SPIN", 0))); ++i)
+    spin.th.emplace_back([&spin] {
+      while (!spin.stop.load(std::memory_order_relaxed)) __builtin_ia32_pause();
+    });
   FullParams params = setup_params(o, syn);
   const Vocab& v = c->ctx->vocab;
   const double user_offset = (o && o->has_offset) ? o->offset : 0.0;
@@ -2292,6 +2287,42 @@ int wdr_dbg_gemm_plan(int32_t fp8, int32_t M, int32_t N, int32_t K, int32_t epi,
     plan_out[1] = p.grid_x;
     plan_out[2] = p.grid_y;
     plan_out[3] = (int32_t)p.lds;
+    return 0;
+  })
+}
+
+int wdr_dbg_cu_mask(int32_t ncu, int32_t n_res, int32_t pat, int32_t only_reserved, uint32_t* words_out,
+                    int32_t n_words) {
+  WDR_GUARD({
+    if (ncu < 1 || ncu > 512 || !words_out || n_words != (ncu + 31) / 32)
+      return fail("cu mask: 1..512 CUs and (ncu + 31) / 32 output words");
+    std::string err;
+    const std::vector<uint32_t> m = cu_mask(ncu, n_res, pat, only_reserved != 0, &err);
+    if (m.empty()) return fail(err);
+    std::copy(m.begin(), m.end(), words_out);
+    return 0;
+  })
+}
+
+int wdr_dbg_stream_plan(int32_t role, int32_t ncu, const int32_t* knobs, wdr_stream_plan* plan_out) {
+  WDR_GUARD({
+    if (role < 0 || role > (int)StreamRole::StateDtw || ncu < 1 || ncu > 512 || !plan_out)
+      return fail("stream plan: a role 0..6, 1..512 CUs and an output");
+    StreamKnobs k;
+    if (knobs)
+      k = StreamKnobs{knobs[0], knobs[1], knobs[2],  knobs[3],       knobs[4],       knobs[5],       knobs[6],
+                      knobs[7], knobs[8], knobs[9],  knobs[10],      knobs[11] != 0, knobs[12] != 0, knobs[13] != 0};
+    else
+      k = stream_knobs_env();
+    const StreamPlan p = stream_plan((StreamRole)role, ncu, k);
+    if (!p.error.empty()) return fail(p.error);
+    *plan_out = wdr_stream_plan{};
+    plan_out->kind = (int32_t)p.kind;
+    plan_out->prio = (int32_t)p.prio;
+    plan_out->pool = p.pool;
+    plan_out->n_words = (int32_t)p.mask.size();
+    std::copy(p.mask.begin(), p.mask.end(), plan_out->mask);
+    snprintf(plan_out->tag, sizeof(plan_out->tag), "%s", p.tag.c_str());
     return 0;
   })
 }

@@ -2,14 +2,9 @@
 // to it; all are tools/gemm_bench on large-v3 shapes, alone on the GPU, unless a bench is named.
 #include "gemm_plan.h"
 
-#include <cstdlib>
+#include "env.h"
 
 namespace wdr {
-
-static int env_int(const char* name, int def) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : def;
-}
 
 GemmKnobs gemm_knobs_env() {
   const GemmKnobs def;

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64) void k_flash_combine(FlashArgs a) {
 }
 
 static int flash_occ() {
-  static const int v = getenv("WDR_FLASH_OCC") && atoi(getenv("WDR_FLASH_OCC")) == 4 ? 4 : 3;
+  static const int v = env_int("WDR_FLASH_OCC", 3) == 4 ? 4 : 3;
   return v;
 }
 

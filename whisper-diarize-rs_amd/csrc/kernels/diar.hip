@@ -171,10 +171,7 @@ __global__ __launch_bounds__(256) void k_gemm32m(Gemm32Args a) {
 
 // the f32 MFMA kernel (default) or the VALU one: WDR_GEMM32=0 at load, or wdr_dbg_set_gemm32
 // (tests/test_gpu_diarize.py compares both within one process)
-static std::atomic<int> g_gemm32_mfma{[] {
-  const char* e = getenv("WDR_GEMM32");
-  return e && atoi(e) == 0 ? 0 : 1;
-}()};
+static std::atomic<int> g_gemm32_mfma{env_on("WDR_GEMM32", true) ? 1 : 0};
 void set_gemm32_mfma(bool on) { g_gemm32_mfma.store(on ? 1 : 0); }
 static bool gemm32_mfma() { return g_gemm32_mfma.load(std::memory_order_relaxed) != 0; }
 

@@ -1023,14 +1023,14 @@ __global__ __launch_bounds__(64) void k_dtw_dp_wave(const float* x, int N, int M
 }
 
 static void launch_dtw_dp(const float* x, int rows, int M, int seek, int* times, int* n_times, hipStream_t s) {
-  static const bool old = getenv("WDR_DTW_DP_OLD") && atoi(getenv("WDR_DTW_DP_OLD")) != 0;   // A/B
+  static const bool old = env_on("WDR_DTW_DP_OLD", false);   // A/B
   if (old) {
     WDR_KLAUNCH(k_dtw_dp, dim3(1), dim3(256), 0, s, x, rows, M, seek, times, n_times);
     return;
   }
   // WDR_DTW_WAVE_MAX = the most rows per lane the one-wave form takes (default 1: it serialises
   // a lane's rows, so above 64 rows the 256-thread form is faster; tools/dtw_bench)
-  static const int rmax = getenv("WDR_DTW_WAVE_MAX") ? atoi(getenv("WDR_DTW_WAVE_MAX")) : 1;
+  static const int rmax = env_int("WDR_DTW_WAVE_MAX", 1);
   const int R = (rows + 63) / 64;
   if (R > rmax) {
     WDR_KLAUNCH(k_dtw_dp, dim3(1), dim3(256), 0, s, x, rows, M, seek, times, n_times);

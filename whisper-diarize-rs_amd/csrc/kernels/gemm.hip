@@ -1517,10 +1517,6 @@ static void launch_epi(const ProjArgs& a, hipStream_t s) {
 // for the residual projections, to share CUs with the encoder GEMM tiles: slower alone --
 // tools/rows_bench, o 15.0 vs 5.1 us, fc2 21.1 vs 13.7 us at 16 rows -- and 5 % slower in the
 // 1-h pipeline, profiles/r04/ab_epi4.txt.)
-static int env_int(const char* name, int def) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : def;
-}
 // WDR_ROWS_PAIR=0: narrow projections of more than 32 rows one row tile per workgroup (A/B; read
 // once)
 static bool rows_pair_tiles() {

@@ -157,8 +157,7 @@ void fatal_handler(int sig, siginfo_t* si, void*) {
 }
 struct FatalInit {
   FatalInit() {
-    const char* e = getenv("WDR_SEGV_TRACE");
-    if (!e || atoi(e) == 0) return;
+    if (!env_on("WDR_SEGV_TRACE", false)) return;
     struct sigaction sa {};
     sa.sa_sigaction = fatal_handler;
     sa.sa_flags = SA_SIGINFO;
@@ -182,8 +181,7 @@ constexpr unsigned kEncEvery = 32;    // full encode batches run eagerly for sam
 // that keeps every launch's probability 1 / (kEvery * kStepEvery)
 static unsigned step_every() {
   static const unsigned v = [] {
-    const char* e = getenv("WDR_PROF_STEP_EVERY");
-    const unsigned n = e ? (unsigned)atoi(e) : 64;
+    const unsigned n = (unsigned)env_int("WDR_PROF_STEP_EVERY", 64);
     return n == 16 || n == 32 ? n : 64;
   }();
   return v;
@@ -224,10 +222,7 @@ int prof_class() { return g_mask.load(); }
 
 std::mutex* launch_lock() {
   static std::mutex mu;
-  static const bool on = [] {
-    const char* e = getenv("WDR_LAUNCH_LOCK");
-    return e && atoi(e) != 0;
-  }();
+  static const bool on = env_on("WDR_LAUNCH_LOCK", false);
   return on ? &mu : nullptr;
 }
 
@@ -278,7 +273,7 @@ void prof_push(int cls, hipEvent_t a, hipEvent_t b, unsigned long long* ts, doub
 }
 
 void stream_note(const char* what, hipStream_t s) {
-  static const bool on = getenv("WDR_STREAM_LOG") && atoi(getenv("WDR_STREAM_LOG")) != 0;
+  static const bool on = env_on("WDR_STREAM_LOG", false);
   if (on) {
     fprintf(stderr, "[wdr-stream] %s %p\n", what, (void*)s);
     fflush(stderr);

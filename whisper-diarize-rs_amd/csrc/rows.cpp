@@ -181,7 +181,7 @@ void rows_forward(const Context& ctx, const RowsIO& io, int R, hipStream_t s, in
   // 12.9 / 13.4 at 56 / 64; fc1 fused 7.3-11.5 vs 8.8-11.6 up to 24 rows, 13.1-16.2 vs 12.2-14.2 at
   // 32-48; the logits split at every count (32 rows: 48.7 vs 83.7 us).
   // WDR_ROWS_LN_FUSE (read once): one threshold for all four (A/B; round 4 fused <= 32 rows).
-  static const int ln_env = getenv("WDR_ROWS_LN_FUSE") ? atoi(getenv("WDR_ROWS_LN_FUSE")) : -1;
+  static const int ln_env = env_int("WDR_ROWS_LN_FUSE", -1);
   const int fuse_qkv = ln_env >= 0 ? ln_env : 48, fuse_xq = ln_env >= 0 ? ln_env : 64,
             fuse_fc1 = ln_env >= 0 ? ln_env : 24, fuse_logits = ln_env >= 0 ? ln_env : 0;
   // pk: this matrix's bit of Model::rows_packed (the weights sit in fragment order)

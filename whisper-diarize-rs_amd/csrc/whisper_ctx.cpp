@@ -5,6 +5,7 @@
 #include "rows.h"
 #include "ggml_file.h"
 #include "prof.h"
+#include "streams.h"
 
 #include <algorithm>
 #include <functional>
@@ -107,212 +108,17 @@ std::recursive_mutex& hip_alloc_mutex() {
   return mu;
 }
 
-// A stream on a hardware queue of its own.  HIP multiplexes the process's streams onto at most
-// GPU_MAX_HW_QUEUES (4) hardware queues per priority level, in order: a kernel of the step batcher
-// then waits behind whatever another stream sharing its queue has in front of it (an encoder GEMM
-// launch, a barrier packet waiting on a slot event).  A stream created with a CU mask gets a
-// dedicated queue; the mask here is every CU of the device.  kind: a WDR_<kind>_HWQ env knob
-// (0 = the shared priority pool, A/B runs), default `def`.
-// WDR_NO_GRAPH: eager decode steps and encode batches (no hipGraph replay); read once
+// WDR_NO_GRAPH: eager decode steps and encode batches (no hipGraph replay); presence alone
+// counts, read once
 static bool no_graph() {
-  static const bool v = getenv("WDR_NO_GRAPH") != nullptr;
+  static const bool v = env_set("WDR_NO_GRAPH");
   return v;
 }
 
-// WDR_HOST_FENCE (default 1): a state's own (decode) stream does not carry barrier packets.  HIP
-// maps the 40 states' highest-priority streams and the step batcher's onto GPU_MAX_HW_QUEUES
-// shared hardware queues, and a queue runs its packets in order: a hipStreamWaitEvent on a state
-// stream waiting for a low-priority DTW pass held back every batched step queued behind it on
-// that queue (configs[2]'s VAD line: long segments, windows encoded on demand on the state
-// stream after such a wait; profiles/r05/vad_line_queues.txt).  The chain's host thread waits
-// for the event instead -- it synchronises on that stream right after anyway.
-// A chain's wait for its encoded window: hipEventQuery every WDR_READY_POLL_US (default 50 us)
-// with the thread asleep in between, instead of hipEventSynchronize, which spins.  At a run's
-// start all 40 chains wait for their first encode batches together (0.1-0.6 s in); spinning, they
-// spent the process's CPU quota (16 CPUs a 100-ms period on the box) in each of those periods and
-// the kernel froze every thread of the process for the rest of it -- 5 throttled periods in a row
-// (bench.py host_cpu.throttle_at_s).  0: hipEventSynchronize.
-static void wait_event_polled(hipEvent_t ev) {
-  static const int us = getenv("WDR_READY_POLL_US") ? atoi(getenv("WDR_READY_POLL_US")) : 50;
-  if (us <= 0) {
-    WDR_HIP(hipEventSynchronize(ev));
-    return;
-  }
-  for (;;) {
-    const hipError_t q = hipEventQuery(ev);
-    if (q == hipSuccess) return;
-    if (q != hipErrorNotReady) WDR_HIP(q);
-    std::this_thread::sleep_for(std::chrono::microseconds(us));
-  }
-}
-
-static bool host_fence() {
-  static const bool v = !(getenv("WDR_HOST_FENCE") && atoi(getenv("WDR_HOST_FENCE")) == 0);
-  return v;
-}
-
-static void stream_fence(hipStream_t s, hipEvent_t ev, bool host) {
-  if (host)
-    WDR_HIP(hipEventSynchronize(ev));
-  else
-    WDR_HIP(hipStreamWaitEvent(s, ev, 0));
-}
-
-hipStream_t dedicated_stream(const char* knob, bool def, int prio) {
-  const char* e = getenv(knob);
-  const bool on = e ? atoi(e) != 0 : def;
-  hipStream_t s = nullptr;
-  if (!on) {
-    WDR_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
-    stream_note(knob, s);
-    return s;
-  }
-  int dev = 0, ncu = 0;
-  WDR_HIP(hipGetDevice(&dev));
-  WDR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-  // knob = 2 (A/B, MI355X): only the CUs the encode-ahead pool leaves free (WDR_ENC_MASK under
-  // WDR_ENC_MASK_PAT=1: 4 per XCD), so this stream's workgroups never wait behind encoder tiles
-  const int n_res = getenv("WDR_ENC_MASK") ? atoi(getenv("WDR_ENC_MASK")) : 32;
-  const bool reserved = atoi(e) == 2 && ncu == 256 && n_res > 0 && n_res <= 32 && n_res % 8 == 0;
-  for (int c = 0; c < ncu; ++c) {
-    const int x = c / 32, r = c % 32;   // the encoder pool's pattern-1 reservation
-    const bool res = r % 8 == x && r / 8 < n_res / 8;
-    if (!reserved || res) mask[c / 32] |= 1u << (c % 32);
-  }
-  WDR_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
-  stream_note(knob, s);
-  return s;
-}
-
-// The encode-ahead streams of all states: WDR_ENC_POOL (default 2) CU-masked streams per device,
-// a dedicated hardware queue each, shared round-robin by the states, which leave WDR_ENC_MASK
-// (default 32) CUs -- 4 per XCD -- to the decode chain.  1-h bench, A/B on one box
-// (profiles/r03/ab_enc_queues.txt): 608-619 xRT with one low-priority stream per state (24 streams
-// on HIP's 4 shared low-priority queues) against 642-646 with 2 or 3 masked queues; 4 or 8
-// masked queues 576, one 547 (the encoder starves), 24 (one per state) 398.  Both knobs -1: one
-// low-priority stream per state.  Returns null then.
-// A stream of a pool of `pool` CU-masked streams (dedicated hardware queues) per (tag, device),
-// handed out round-robin, that leave n_res CUs free (WDR_ENC_MASK_PAT=1: spread over the 8 XCDs
-// whether mask bit c is CU c % 32 of XCD c / 32 or CU c / 8 of XCD c % 8 -- bits 32x + 8j + x,
-// j < n/8 -- since a decode launch's workgroups go round-robin over the XCDs, every XCD needs free
-// CUs; 0: the top n bits).  pool <= 0: a stream of its own.
-using StreamPools = std::map<std::pair<std::string, int>, std::pair<std::vector<hipStream_t>, int>>;
-static std::mutex& stream_pools_mu() {
-  static std::mutex mu;
-  return mu;
-}
-static StreamPools& stream_pools() {
-  static StreamPools* p = new StreamPools();   // outlives static destruction (exit hook)
-  return *p;
-}
-
-void destroy_stream_pools() {
-  std::lock_guard<std::mutex> g(stream_pools_mu());
-  for (auto& kv : stream_pools()) {
-    (void)hipSetDevice(kv.first.second);
-    for (hipStream_t st : kv.second.first) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  }
-  stream_pools().clear();
-  (void)hipGetLastError();
-}
-
-static hipStream_t masked_pool_stream(const char* tag, int n_res, int pool, bool* shared) {
-  int dev = 0, ncu = 0;
-  WDR_HIP(hipGetDevice(&dev));
-  WDR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  WDR_CHECK(n_res < ncu, "masked stream: must leave at least one CU");
-  static const int pat = getenv("WDR_ENC_MASK_PAT") ? atoi(getenv("WDR_ENC_MASK_PAT")) : 1;
-  auto make = [&] {
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    std::vector<char> res(ncu, 0);
-    if (pat == 1 && ncu == 256) {
-      WDR_CHECK(n_res % 8 == 0 && n_res <= 32, "WDR_ENC_MASK_PAT=1: 0, 8, 16, 24 or 32 CUs");
-      for (int x = 0; x < 8; ++x)
-        for (int j = 0; j < std::max(0, n_res) / 8; ++j) res[32 * x + 8 * j + x] = 1;
-    } else {
-      for (int c = ncu - std::max(0, n_res); c < ncu; ++c) res[c] = 1;
-    }
-    for (int c = 0; c < ncu; ++c)
-      if (!res[c]) mask[c / 32] |= 1u << (c % 32);
-    hipStream_t st = nullptr;
-    WDR_HIP(hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()));
-    stream_note(tag, st);
-    return st;
-  };
-  *shared = false;
-  if (pool <= 0) return make();
-  std::lock_guard<std::mutex> g(stream_pools_mu());
-  auto& P = stream_pools()[{tag, dev}];
-  if (P.first.empty())
-    for (int i = 0; i < pool; ++i) P.first.push_back(make());
-  *shared = true;
-  return P.first[P.second++ % pool];
-}
-
-// The encode-ahead streams of all states: WDR_ENC_POOL (default 2) CU-masked streams per device,
-// a dedicated hardware queue each, shared round-robin by the states, which leave WDR_ENC_MASK
-// (default 32) CUs -- 4 per XCD -- to the decode chain.  1-h bench, A/B on one box
-// (profiles/r03/ab_enc_queues.txt): 608-619 xRT with one low-priority stream per state (24 streams
-// on HIP's 4 shared low-priority queues) against 642-646 with 2 or 3 masked queues; 4 or 8
-// masked queues 576, one 547 (the encoder starves), 24 (one per state) 398.  Both knobs -1: one
-// low-priority stream per state.  Returns null then.
-static hipStream_t enc_masked_stream(bool* shared) {
-  static const int n_res = getenv("WDR_ENC_MASK") ? atoi(getenv("WDR_ENC_MASK")) : 32;
-  static const int pool = getenv("WDR_ENC_POOL") ? atoi(getenv("WDR_ENC_POOL")) : 2;
-  *shared = false;
-  if (n_res < 0 && pool < 0) return nullptr;
-  int dev = 0, ncu = 0;
-  WDR_HIP(hipGetDevice(&dev));
-  WDR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (ncu != 256 && !getenv("WDR_ENC_MASK") && !getenv("WDR_ENC_POOL")) return nullptr;   // tuned on MI355X
-  return masked_pool_stream("enc", n_res, pool, shared);
-}
-
-// One mutex per pooled stream: a state's encode batch is issued onto a shared stream as one
-// unit, so batches run one after another instead of interleaving kernel by kernel (at the start
-// of a run every state issues its first batch at once: interleaved, all 12 batches of a stream
-// finished together, ~0.6 s in; one after another, the first chains start decoding ~50 ms in).
-static std::mutex& stream_issue_mutex(hipStream_t st) {
-  static std::mutex mu;
-  static std::map<hipStream_t, std::unique_ptr<std::mutex>> m;
-  std::lock_guard<std::mutex> g(mu);
-  auto& p = m[st];
-  if (!p) p = std::make_unique<std::mutex>();
-  return *p;
-}
-
-// WDR_OWN_POOL=P (A/B): the states' own streams from P masked streams (WDR_OWN_MASK CUs left
-// free, default 0) instead of one highest-priority stream each, so no chain's own work (on-demand
-// encodes, fix-up passes) shares the step batcher's hardware queue.  Null when unset.
-static hipStream_t own_masked_stream(bool* shared) {
-  static const int pool = getenv("WDR_OWN_POOL") ? atoi(getenv("WDR_OWN_POOL")) : -1;
-  static const int n_res = getenv("WDR_OWN_MASK") ? atoi(getenv("WDR_OWN_MASK")) : 0;
-  *shared = false;
-  if (pool < 0) return nullptr;
-  return masked_pool_stream("own", n_res, pool, shared);
-}
-
-// WDR_ODM_POOL (default 4): a long segment's later windows (encoded on demand: they depend on
-// the decoded seek) run on P CU-masked streams (dedicated hardware queues, WDR_ODM_MASK CUs left
-// free, default 32 as the encode-ahead pool), not on the state's own highest-priority stream.  A
-// window's encoder (~70 launches, several ms) on the state stream shared a hardware queue with
-// the step batcher, which runs its packets in order, so every batched step queued behind it
-// waited (configs[2]'s VAD line: long merged segments; profiles/r05/vad_line_queues.txt,
-// profiles/r06/ab_lines_hwq.txt).  -1: the state stream (as before).
-static hipStream_t odm_masked_stream(bool* shared) {
-  static const int pool = getenv("WDR_ODM_POOL") ? atoi(getenv("WDR_ODM_POOL")) : 4;
-  static const int n_res = getenv("WDR_ODM_MASK") ? atoi(getenv("WDR_ODM_MASK")) : 32;
-  *shared = false;
-  if (pool < 0) return nullptr;
-  int dev = 0, ncu = 0;
-  WDR_HIP(hipGetDevice(&dev));
-  WDR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (ncu != 256 && !getenv("WDR_ODM_POOL")) return nullptr;   // tuned on MI355X
-  return masked_pool_stream("odm", n_res, pool, shared);
+// the placement knobs the states' streams follow: read once per process, when the first state is made
+static const StreamKnobs& state_stream_knobs() {
+  static const StreamKnobs k = stream_knobs_env();
+  return k;
 }
 
 DevMem::DevMem(size_t n) : bytes(n) {
@@ -391,21 +197,12 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
   WDR_CHECK(cp.use_gpu, "libwdr has no CPU backend: use_gpu=false is not supported (the CPU restatement is test-only)");
   WDR_HIP(hipSetDevice(cp.gpu_device));
   {
-    // the latency-bound decode chain runs at the highest priority; the encode-ahead
-    // stream (State) fills the CUs it leaves idle
-    int lo = 0, hi = 0;
-    WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    WDR_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-    stream_note("context", stream);
+    // the context's own stream: placement knobs play no part in it
+    stream = open_stream(StreamRole::Context, StreamKnobs()).s;
     // WDR_PRIME_LOWQ (A/B): a lowest-priority stream created -- and its hardware queue
-    // instantiated by one launch -- right after the context's own, before the step batcher's
+    // instantiated by one memset -- right after the context's own, before the step batcher's
     // and the states' streams
-    if (getenv("WDR_PRIME_LOWQ") && atoi(getenv("WDR_PRIME_LOWQ")) != 0) {
-      WDR_HIP(hipStreamCreateWithPriority(&low_prime, hipStreamNonBlocking, lo));
-      DevMem one(16);
-      WDR_HIP(hipMemsetAsync(one.p, 0, 16, low_prime));
-      WDR_HIP(hipStreamSynchronize(low_prime));
-    }
+    if (env_on("WDR_PRIME_LOWQ", false)) low_prime = prime_queue(StreamPrio::Lowest);
     // Hardware queues in a fixed order (WDR_PRIME_POOLS, default "lnh" on MI355X; "0" = off):
     // HIP serves each stream priority from a pool of 4 hardware queues; which of them first carried
     // work, and in what order, followed whichever thread launched first -- and that order set a
@@ -418,27 +215,21 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
     // configs[2]'s VAD line at 882-895 xRT; highest first (hnl / hln) runs both at 715-742;
     // lowest only fixes the VAD line (883) and costs the diarized one (754) -- the spread the
     // stream-placement experiments of this round kept landing on.
-    const char* po_env = getenv("WDR_PRIME_POOLS");
+    const char* po_env = env_str("WDR_PRIME_POOLS");
     int ncu_p = 0;
     WDR_HIP(hipDeviceGetAttribute(&ncu_p, hipDeviceAttributeMultiprocessorCount, cp.gpu_device));
     const char* po = po_env ? po_env : (ncu_p == 256 ? "lnh" : "");
     if (po[0] && std::string(po) != "0") {
       DevMem sink(4096);
       for (const char* c = po; *c; ++c) {
-        for (int k = 0; k < 4; ++k) {
-          hipStream_t ps = nullptr;
-          if (*c == 'n') WDR_HIP(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
-          else WDR_HIP(hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, *c == 'l' ? lo : hi));
-          WDR_CHECK(*c == 'l' || *c == 'n' || *c == 'h', "WDR_PRIME_POOLS: letters l / n / h");
-          stream_note(*c == 'l' ? "prime-low" : *c == 'n' ? "prime-normal" : "prime-high", ps);
-          launch_busy(1, 1000, sink.as<float>(), ps);
-          prime_streams.push_back(ps);
-        }
+        WDR_CHECK(*c == 'l' || *c == 'n' || *c == 'h', "WDR_PRIME_POOLS: letters l / n / h");
+        for (int k = 0; k < 4; ++k)
+          prime_streams.push_back(*c == 'l'   ? prime_queue(StreamPrio::Lowest, "prime-low", sink.as<float>())
+                                  : *c == 'n' ? prime_queue(StreamPrio::None, "prime-normal", sink.as<float>())
+                                              : prime_queue(StreamPrio::Highest, "prime-high", sink.as<float>()));
       }
       for (hipStream_t ps : prime_streams) WDR_HIP(hipStreamSynchronize(ps));
     }
-    // WDR_DTWQ_EARLY (A/B): the DTW queue (its lowest-priority stream) made at the end of the
-    // constructor, before the batcher and the states
   }
   Model& m = model;
   m.hp = hp;
@@ -644,7 +435,7 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
   // alone at any row count (profiles/r07/rows_bench_packed.txt)
   DevMem pscratch;
   {
-    const char* pe = getenv("WDR_ROWS_PACKED");
+    const char* pe = env_str("WDR_ROWS_PACKED");
     m.rows_packed = pe ? (unsigned)strtoul(pe, nullptr, 0) & 0x7f : 0x7fu;
     if (m.rows_packed & 0x3f) pscratch = DevMem((size_t)4 * dt * dt * 2);
     auto pack = [&](f16* w, int N, int K) {
@@ -672,12 +463,10 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
   pscratch = DevMem();   // freed under hip_alloc_mutex (DevMem)
   {
     // KV pool for the decode chains of every State of this context (multi-chain pipeline)
-    const char* e = getenv("WDR_DECODE_CHAINS");
-    max_chains = std::max(1, std::min(64, e ? atoi(e) : 40));   // 24 -> 40: +2.6 % (profiles/r04/ab_chains*.txt)
-    const char* nb = getenv("WDR_BATCHERS");
-    n_batchers = std::max(1, std::min(8, nb ? atoi(nb) : 1));
-    prefill_split = getenv("WDR_PREFILL_SPLIT") && atoi(getenv("WDR_PREFILL_SPLIT")) != 0;
-    fp8_encoder = getenv("WDR_FP8_ENCODER") && atoi(getenv("WDR_FP8_ENCODER")) != 0;
+    max_chains = std::max(1, std::min(64, env_int("WDR_DECODE_CHAINS", 40)));   // 24 -> 40: +2.6 % (profiles/r04/ab_chains*.txt)
+    n_batchers = std::max(1, std::min(8, env_int("WDR_BATCHERS", 1)));
+    prefill_split = env_on("WDR_PREFILL_SPLIT", false);
+    fp8_encoder = env_on("WDR_FP8_ENCODER", false);
     fp8_plan = fp8_plan_for(hp.n_audio_layer);
     const size_t per = (size_t)hp.n_text_layer * 21 * hp.n_text_ctx * hp.n_text_state;   // NSLOT = 21
     kv_k = DevMem(per * max_chains * 2);
@@ -685,7 +474,9 @@ Context::Context(const std::string& model_name, const HParams& hp, const Context
     kv_seq_stride = (long long)hp.n_text_ctx * hp.n_text_state;
     kv_layer_stride = (long long)max_chains * 21 * kv_seq_stride;
   }
-  if (getenv("WDR_DTWQ_EARLY") && atoi(getenv("WDR_DTWQ_EARLY")) != 0 && !aheads.empty()) {
+  // WDR_DTWQ_EARLY (A/B): the DTW queue (its lowest-priority stream) made at the end of the
+  // constructor, before the batcher and the states
+  if (env_on("WDR_DTWQ_EARLY", false) && !aheads.empty()) {
     DtwQueue& q = dtw_queue();
     (void)q;
   }
@@ -740,9 +531,8 @@ struct State::Impl {
   DevMem xkv_ring;
   size_t xkv_slot_elems = 0;
   int cur = 0;                // slot the decoder reads (cross-K/V, samples)
-  bool own_shared = false;    // own from the WDR_OWN_POOL pool
-  bool es_shared = false;     // es from the WDR_ENC_MASK pool (not destroyed with the state)
-  hipStream_t es = nullptr;   // encode-ahead stream (lower priority than the decode stream)
+  StreamRef es;               // encode-ahead stream (lower priority than the decode stream; shared:
+                              // from the WDR_ENC_POOL pool, not destroyed with the state)
   struct Plan {
     std::vector<const int16_t*> pcm;
     std::vector<int> n;
@@ -762,7 +552,7 @@ struct State::Impl {
     std::unique_ptr<RowBatch> tl;
   };
   std::map<int, EncGraph> enc_graphs;
-  hipStream_t es_cap = nullptr;   // the stream those graphs are captured on (never launched on)
+  StreamRef es_cap;               // the stream those graphs are captured on (never launched on)
   // WDR_CHAIN_LOG: DTW-queue waits / encoder launch host time (ns; the encode-ahead thread adds too)
   std::atomic<long long> t_fence{0}, t_enc_launch{0};
   // the encode-ahead host thread: issues the plan's batches (top_up_batch) up to the lookahead of
@@ -808,15 +598,14 @@ struct State::Impl {
   f16* vc = nullptr;
   int nslot_tot = 0;          // sequences per layer in the pool (layer stride / seq_stride)
   long long seq_stride = 0;   // elements per (layer, seq)
-  hipStream_t own = nullptr;  // this state's decode stream
-  hipStream_t eo = nullptr;   // on-demand window encodes (WDR_ODM_POOL; null: the decode stream)
-  bool eo_shared = false;
+  StreamRef own;              // this state's decode stream (shared: from the WDR_OWN_POOL pool)
+  StreamRef eo;               // on-demand window encodes (WDR_ODM_POOL; null: the decode stream)
   // dtw
   DevMem nrm, xdtw, times;
   struct DtwSet {
     DevMem cap, nrm, xdtw, times;
   } dset;
-  hipStream_t sd = nullptr;        // DTW stream
+  StreamRef sd;                    // DTW stream
   hipEvent_t ev_sync = nullptr;    // decode-stream point the DTW stream waits for
   hipEvent_t ev_dtw = nullptr;     // last DTW job enqueued (on-demand encodes wait for it)
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;   // prompt-prefill timing
@@ -860,7 +649,7 @@ struct State::Impl {
 // and the last WDR_FP8_F16_TAIL, which stay f16.
 std::vector<uint8_t> fp8_plan_for(int n_layer) {
   std::vector<uint8_t> plan(n_layer, 0xf);
-  if (const char* e = getenv("WDR_FP8_PLAN"); e && *e) {
+  if (const char* e = env_str("WDR_FP8_PLAN"); e && *e) {
     uint8_t last = 0xf;
     for (int l = 0; l < n_layer; ++l) {
       if (e[l] && isxdigit((unsigned char)e[l])) {
@@ -877,9 +666,10 @@ std::vector<uint8_t> fp8_plan_for(int n_layer) {
     }
     return plan;
   }
-  const uint8_t proj = getenv("WDR_FP8_PROJ") ? (uint8_t)(strtol(getenv("WDR_FP8_PROJ"), nullptr, 16) & 0xf) : 0xf;
-  const int head = getenv("WDR_FP8_F16_HEAD") ? atoi(getenv("WDR_FP8_F16_HEAD")) : 0;
-  const int tail = getenv("WDR_FP8_F16_TAIL") ? atoi(getenv("WDR_FP8_F16_TAIL")) : 0;
+  const char* pe = env_str("WDR_FP8_PROJ");   // a hex nibble
+  const uint8_t proj = pe ? (uint8_t)(strtol(pe, nullptr, 16) & 0xf) : 0xf;
+  const int head = env_int("WDR_FP8_F16_HEAD", 0);
+  const int tail = env_int("WDR_FP8_F16_TAIL", 0);
   for (int l = 0; l < n_layer; ++l) plan[l] = (l < head || l >= n_layer - tail) ? 0 : proj;
   return plan;
 }
@@ -925,8 +715,7 @@ static constexpr int kSlots = 16;    // in-flight segments in the cross-K/V ring
 // above (large-v3: 40 chains x 9 slots x 245.8 MB = 88 GB of cross-K/V; 48 chains of 17 slots
 // did not fit in 288 GB beside the KV pool, profiles/r04/ab_flash_occ.txt)
 static int ring_slots(int max_chains) {
-  const char* e = getenv("WDR_SLOTS");
-  const int n = e ? atoi(e) / kBatch * kBatch : max_chains > 24 ? 8 : kSlots;
+  const int n = env_set("WDR_SLOTS") ? env_int("WDR_SLOTS", 0) / kBatch * kBatch : max_chains > 24 ? 8 : kSlots;
   return std::max(kBatch, std::min(kSlots, n));
 }
 
@@ -954,15 +743,7 @@ State::State(Context& ctx, int chain_) : ctx_(ctx), s_(nullptr), m_(new Impl) {
   chain = chain_;
   WDR_CHECK(chain >= 0 && chain < ctx.max_chains, "decode chain index out of range");
   {
-    // every state has its own highest-priority decode stream (chains run concurrently)
-    int lo = 0, hi = 0;
-    WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    // WDR_OWN_PRIO=1|2 (A/B): the state's own stream at the normal / lowest priority
-    static const int op = getenv("WDR_OWN_PRIO") ? atoi(getenv("WDR_OWN_PRIO")) : 0;
-    m.own = own_masked_stream(&m.own_shared);
-    if (m.own) {
-    } else if (op == 1) WDR_HIP(hipStreamCreateWithFlags(&m.own, hipStreamNonBlocking));
-    else WDR_HIP(hipStreamCreateWithPriority(&m.own, hipStreamNonBlocking, op == 2 ? lo : hi));
+    m.own = open_stream(StreamRole::StateOwn, state_stream_knobs());
     s_ = m.own;
     stream_note("state-own", s_);
   }
@@ -986,16 +767,9 @@ State::State(Context& ctx, int chain_) : ctx_(ctx), s_(nullptr), m_(new Impl) {
   m.xkv_ring = DevMem((m.S + 2) * m.xkv_slot_elems * 2);   // + the on-demand spare (xsel)
   m.cur = m.S;
   {
-    // the encode-ahead stream at the lowest priority (WDR_ENC_PRIO=1: the middle of the range,
-    // 2: the highest; A/B runs)
-    int lo = 0, hi = 0;
-    WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    static const int ep = getenv("WDR_ENC_PRIO") ? atoi(getenv("WDR_ENC_PRIO")) : 0;
-    const int prio = ep == 2 ? hi : ep == 1 ? (lo + hi) / 2 : lo;
-    m.es = enc_masked_stream(&m.es_shared);
-    if (!m.es) WDR_HIP(hipStreamCreateWithPriority(&m.es, hipStreamNonBlocking, prio));
+    m.es = open_stream(StreamRole::StateEncAhead, state_stream_knobs());
     stream_note("state-es", m.es);
-    m.eo = odm_masked_stream(&m.eo_shared);
+    m.eo = open_stream(StreamRole::StateOnDemand, state_stream_knobs());
   }
   // this state's rows forwards: prompt prefills / DTW re-forwards up to RMAX rows, steps of up
   // to NSEQ logit rows; the DTW set captures; language detection kBatch rows
@@ -1029,10 +803,7 @@ State::State(Context& ctx, int chain_) : ctx_(ctx), s_(nullptr), m_(new Impl) {
     D.times = DevMem((RMAX + 8) * 4);
     WDR_HIP(hipHostMalloc((void**)&m.h_lang, (size_t)(kSlots + 1) * 100 * 4, hipHostMallocDefault));
     m.lang_src.assign(kSlots + 1, -1);
-    int lo = 0, hi = 0;
-    WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    WDR_HIP(hipStreamCreateWithPriority(&m.sd, hipStreamNonBlocking, lo));
-    stream_note("state-sd", m.sd);
+    m.sd = open_stream(StreamRole::StateDtw, state_stream_knobs());
     WDR_HIP(hipEventCreateWithFlags(&m.ev_sync, hipEventDisableTiming));
     WDR_HIP(hipEventCreateWithFlags(&m.ev_dtw, hipEventDisableTiming));
     WDR_HIP(hipEventCreate(&m.ev_p0));
@@ -1069,28 +840,16 @@ State::~State() {
     if (m_->es) (void)hipStreamSynchronize(m_->es);
     for (auto& g : m_->enc_graphs)
       if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    if (m_->es_cap) (void)hipStreamDestroy(m_->es_cap);
+    if (m_->es_cap.s) (void)hipStreamDestroy(m_->es_cap.s);
     (void)hipHostFree(m_->h_tok);
     (void)hipHostFree(m_->h_ctl);
     (void)hipHostFree(m_->h_times);
     (void)hipHostFree(m_->h_beam);
     (void)hipHostFree(m_->h_pairs);
-    if (m_->es) {
-      (void)hipStreamSynchronize(m_->es);
-      if (!m_->es_shared) (void)hipStreamDestroy(m_->es);
-    }
-    if (m_->sd) {
-      (void)hipStreamSynchronize(m_->sd);
-      (void)hipStreamDestroy(m_->sd);
-    }
-    if (m_->own) {
-      (void)hipStreamSynchronize(m_->own);
-      if (!m_->own_shared) (void)hipStreamDestroy(m_->own);
-    }
-    if (m_->eo) {
-      (void)hipStreamSynchronize(m_->eo);
-      if (!m_->eo_shared) (void)hipStreamDestroy(m_->eo);
-    }
+    close_stream(m_->es);
+    close_stream(m_->sd);
+    close_stream(m_->own);
+    close_stream(m_->eo);
     for (auto& j : m_->jobs) {
       if (j.blk) m_->blk_pool.push_back(j.blk);
       if (j.done) m_->ev_pool.push_back(j.done);
@@ -1296,7 +1055,7 @@ hipStream_t State::encode_window(int seek) {
   }
   // a shared stream: the window's launches issued as one unit (as the encode-ahead batches)
   std::unique_lock<std::mutex> issue_lk;
-  if (m.eo_shared) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.eo));
+  if (m.eo.shared) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.eo));
   Im2colMelArgs ia{sl.mel.as<float>(), m.n_mels, sl.n_fft_frames, sl.gmax.as<int>(), seek, m.kp1, m.e1.im2col.as<f16>()};
   launch_im2col_mel(ia, s);
   encoder_body(ctx_, m, m.e1, 1, const_cast<f16*>(m.xkv()), s);
@@ -1395,10 +1154,7 @@ void State::unplan() {
 // with no detection pass on the encode stream (lang_first) measured 835.1 vs 810.9 xRT, 4 of 4
 // pairs ahead (profiles/r05/ab_ahead6_langfirst0.txt).
 static int enc_ahead(int S) {
-  static const int a = [] {
-    const char* e = getenv("WDR_ENC_AHEAD");
-    return e ? atoi(e) : 6;
-  }();
+  static const int a = env_int("WDR_ENC_AHEAD", 6);
   return std::max(kBatch, std::min(a > 0 ? a : S, S));
 }
 
@@ -1417,7 +1173,7 @@ void State::slot_dtw_fence(int k, hipStream_t s) {
 
 // WDR_ODM_ALT (default 1; read once): see Impl::xsel
 static bool odm_alt() {
-  static const bool v = !(getenv("WDR_ODM_ALT") && atoi(getenv("WDR_ODM_ALT")) == 0);
+  static const bool v = env_on("WDR_ODM_ALT", true);
   return v;
 }
 
@@ -1444,7 +1200,7 @@ void State::dtw_queue_fence(hipStream_t s) {
 }
 
 static bool enc_thread_on() {
-  static const bool on = !(getenv("WDR_ENC_THREAD") && atoi(getenv("WDR_ENC_THREAD")) == 0);
+  static const bool on = env_on("WDR_ENC_THREAD", true);
   return on;
 }
 
@@ -1516,7 +1272,7 @@ void State::top_up(int j) {
 // their own on the encode-ahead stream per 4-window batch; the same arithmetic, so the same
 // language logits
 static bool lang_piggyback() {
-  static const bool on = !(getenv("WDR_LANG_PIGGYBACK") && atoi(getenv("WDR_LANG_PIGGYBACK")) == 0);
+  static const bool on = env_on("WDR_LANG_PIGGYBACK", true);
   return on;
 }
 
@@ -1526,7 +1282,7 @@ static bool lang_piggyback() {
 // (alone: profiles/r05/ab_lang_first.txt, 855.4 vs 848.2 xRT, inside the +-1.5 % bar; with the
 // 6-segment encode-ahead, enc_ahead: 835.1 vs 810.9, ab_ahead6_langfirst0.txt)
 static bool lang_first() {
-  static const bool on = getenv("WDR_LANG_FIRST") && atoi(getenv("WDR_LANG_FIRST")) != 0;
+  static const bool on = env_on("WDR_LANG_FIRST", false);
   return on;
 }
 
@@ -1544,11 +1300,7 @@ bool State::top_up_batch(int j) {
   // look-ahead batches queued at once the first batches finished late (1-h bench, chain log:
   // 0.58 -> 0.46 s per chain).  A first batch of 1 or 2 windows (WDR_ENC_FIRST) measured slower
   // (570 / 580 vs 624 xRT: partial, ungraphed batches and a misaligned ring).
-  static const int first = [] {
-    const char* e = getenv("WDR_ENC_FIRST");
-    const int v = e ? atoi(e) : kBatch;
-    return std::max(1, std::min(kBatch, v));
-  }();
+  static const int first = std::max(1, std::min(kBatch, env_int("WDR_ENC_FIRST", kBatch)));
   {
     if ((int)m.plan.next_enq >= N) return false;
     const int g0 = (int)m.plan.next_enq;
@@ -1559,9 +1311,9 @@ bool State::top_up_batch(int j) {
       WDR_HIP(hipEventSynchronize(m.slots[(g0 - 1) % m.S].ready));   // the first window encoded
     const int slot0 = g0 % m.S;
     // a shared (pooled) encode stream: the whole batch issued as one unit (WDR_ENC_ATOMIC=0: A/B)
-    static const bool atomic_issue = !(getenv("WDR_ENC_ATOMIC") && atoi(getenv("WDR_ENC_ATOMIC")) == 0);
+    static const bool atomic_issue = env_on("WDR_ENC_ATOMIC", true);
     std::unique_lock<std::mutex> issue_lk;
-    if (m.es_shared && atomic_issue) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.es));
+    if (m.es.shared && atomic_issue) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.es));
     for (int k = g0; k < g1; ++k) {
       Impl::Slot& sl = m.slots[k % m.S];
       if (k >= m.S) WDR_HIP(hipStreamWaitEvent(m.es, sl.freed, 0));
@@ -1639,7 +1391,7 @@ bool State::top_up_batch(int j) {
       std::atomic<long long>& acc;
       ~ElT() { acc += (long long)((now_s() - t0) * 1e9); }
     } el_t{t_el, m.t_enc_launch};
-    static const bool enc_graph = !(getenv("WDR_ENC_GRAPH") && atoi(getenv("WDR_ENC_GRAPH")) == 0);
+    static const bool enc_graph = env_on("WDR_ENC_GRAPH", true);
     // the live profiler (bench.py's roofline) samples eager launches only: while it is on, 1 in
     // kEncEvery graphable batches runs eagerly with its launches sampled at the matching rate
     // (prof.h); partial batches, always eager, are sampled at the base rate -- a uniform sample
@@ -1655,33 +1407,14 @@ bool State::top_up_batch(int j) {
           (void)ctx_.fp8_layers();
         }
         if (!eg.tl) eg.tl = std::make_unique<RowBatch>(kBatch, kBatch, 0);
-        std::lock_guard<std::recursive_mutex> cap_lock(hip_alloc_mutex());   // no allocation meanwhile
+        std::lock_guard<std::recursive_mutex> cap_lock(hip_alloc_mutex());   // the stream's creation too
         // captured on a stream of its own: the chain thread waits on events recorded on m.es,
         // which HIP refuses while m.es itself is capturing
-        if (!m.es_cap) WDR_HIP(hipStreamCreateWithFlags(&m.es_cap, hipStreamNonBlocking));
+        if (!m.es_cap) WDR_HIP(hipStreamCreateWithFlags(&m.es_cap.s, hipStreamNonBlocking));
         stream_note("state-es_cap", m.es_cap);
-        hipGraph_t graph;
-        prof_capture(true);
-        WDR_HIP(hipStreamBeginCapture(m.es_cap, hipStreamCaptureModeRelaxed));
-        try {
-          body(*eg.tl, true, m.es_cap);
-        } catch (...) {
-          hipGraph_t dead = nullptr;
-          (void)hipStreamEndCapture(m.es_cap, &dead);
-          if (dead) (void)hipGraphDestroy(dead);
-          prof_capture(false);
-          throw;
-        }
-        prof_capture(false);
-        WDR_HIP(hipStreamEndCapture(m.es_cap, &graph));
-        WDR_HIP(hipGraphInstantiate(&eg.exec, graph, nullptr, nullptr, 0));
-        WDR_HIP(hipGraphDestroy(graph));
+        eg.exec = capture_exec(m.es_cap, [&] { body(*eg.tl, true, m.es_cap); });
       }
-      std::mutex* mu = launch_lock();   // WDR_LAUNCH_LOCK (prof.h)
-      if (mu) mu->lock();
-      const hipError_t ge = hipGraphLaunch(eg.exec, m.es);
-      if (mu) mu->unlock();
-      WDR_HIP(ge);
+      replay(eg.exec, m.es);
     } else {
       prof_in_enc(sampled);
       try {
@@ -1716,10 +1449,7 @@ bool State::top_up_batch(int j) {
 // WDR_DTW_QUEUE=0: multi-chain DTW re-forwards ride in the step batcher's requests (the round-3
 // schedule) instead of the DtwQueue
 static bool dtw_queue_on() {
-  static const bool on = [] {
-    const char* e = getenv("WDR_DTW_QUEUE");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool on = env_on("WDR_DTW_QUEUE", true);
   return on;
 }
 
@@ -1766,10 +1496,21 @@ void State::prefill_on(const int* toks, int n, int seq, bool want_logits, bool c
   if (st == s_) times.prefills++;
 }
 
-// R decoder rows of this state (beams / best_of decoders, chain-local sequences seqs[r]) reading
-// the current slot: one group sharing the slot, logits of every row into mb.logits
-void State::decoder_step(const int* toks, const int* seqs, const int* pos, int R) {
-  Impl& m = *m_;
+// a sampled token as the decode loop keeps it (timestamps and DTW fields filled in later)
+static TokenData token_data(const TokOut& o) {
+  TokenData t;
+  t.id = o.id;
+  t.tid = o.tid;
+  t.p = o.p;
+  t.plog = o.plog;
+  t.pt = o.pt;
+  t.ptsum = o.ptsum;
+  return t;
+}
+
+// the row table of a decode step: R rows of `chain` (chain-local sequences seqs[r]) as one group
+// sharing the current slot, logits of every row
+static RowBatch& step_rows(State::Impl& m, int chain, const int* toks, const int* seqs, const int* pos, int R) {
   WDR_CHECK(R >= 1 && R <= NSEQ, "decoder step: row count out of range");
   RowBatch& tb = *m.tb;
   tb.clear();
@@ -1783,6 +1524,14 @@ void State::decoder_step(const int* toks, const int* seqs, const int* pos, int R
   g.xkv = m.xkv();
   g.logits = 2;
   tb.add(g);
+  return tb;
+}
+
+// R decoder rows of this state (beams / best_of decoders) reading the current slot, logits of
+// every row into mb.logits
+void State::decoder_step(const int* toks, const int* seqs, const int* pos, int R) {
+  Impl& m = *m_;
+  RowBatch& tb = step_rows(m, chain, toks, seqs, pos, R);
   RowsIO io = m.mb.io(ctx_, m.V);
   tb.upload(io, s_, true, true);
   rows_forward(ctx_, io, R, s_);
@@ -1812,18 +1561,7 @@ void State::step_and_sample(const int* toks, const int* seqs, const int* pos, co
     if (K > 0) logits_topk(R, K, cands);
     return;
   }
-  RowBatch& tb = *m.tb;
-  tb.clear();
-  int sq[NSEQ];
-  for (int i = 0; i < R; ++i) sq[i] = chain * NSLOT + seqs[i];
-  RowGroupDesc grp;
-  grp.n = R;
-  grp.tok = toks;
-  grp.seq = sq;
-  grp.pos = pos;
-  grp.xkv = m.xkv();
-  grp.logits = 2;
-  tb.add(grp);
+  RowBatch& tb = step_rows(m, chain, toks, seqs, pos, R);
   memcpy(m.h_ctl, ctl, R * sizeof(LogitsCtl));
   RowsIO io = m.mb.io(ctx_, m.V);
   Impl::StepGraph& g = m.graphs[(K << 16) + R];
@@ -1832,49 +1570,27 @@ void State::step_and_sample(const int* toks, const int* seqs, const int* pos, co
     g.exec = nullptr;
   }
   if (!g.exec) {
-    std::lock_guard<std::recursive_mutex> cap_lock(hip_alloc_mutex());   // no allocation meanwhile
-    hipGraph_t graph;
-    prof_capture(true);
-    WDR_HIP(hipStreamBeginCapture(s_, hipStreamCaptureModeRelaxed));
-    tb.upload(io, s_, true, false);
-    WDR_HIP(wdr_memcpy_async(m.ctl.p, m.h_ctl, R * sizeof(LogitsCtl), hipMemcpyHostToDevice, s_));
-    rows_forward(ctx_, io, R, s_);
-    launch_logits_process(m.mb.logits.as<float>(), m.V, m.ctl.as<LogitsCtl>(), m.vids, R, m.work.as<float>(),
-                          m.tokout.as<TokOut>(), s_);
-    WDR_HIP(wdr_memcpy_async(m.h_tok, m.tokout.p, R * sizeof(TokOut), hipMemcpyDeviceToHost, s_));
-    if (K > 0) {
-      launch_logits_topk(m.mb.logits.as<float>(), m.V, m.ctl.as<LogitsCtl>(), m.vids, R, K, m.work.as<float>(),
-                         m.beamc.as<BeamCand>(), s_);
-      WDR_HIP(wdr_memcpy_async(m.h_beam, m.beamc.p, (size_t)R * K * sizeof(BeamCand), hipMemcpyDeviceToHost, s_));
-    }
-    prof_capture(false);
-    WDR_HIP(hipStreamEndCapture(s_, &graph));
-    WDR_HIP(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-    WDR_HIP(hipGraphDestroy(graph));
+    g.exec = capture_exec(s_, [&] {
+      tb.upload(io, s_, true, false);
+      WDR_HIP(wdr_memcpy_async(m.ctl.p, m.h_ctl, R * sizeof(LogitsCtl), hipMemcpyHostToDevice, s_));
+      rows_forward(ctx_, io, R, s_);
+      launch_logits_process(m.mb.logits.as<float>(), m.V, m.ctl.as<LogitsCtl>(), m.vids, R, m.work.as<float>(),
+                            m.tokout.as<TokOut>(), s_);
+      WDR_HIP(wdr_memcpy_async(m.h_tok, m.tokout.p, R * sizeof(TokOut), hipMemcpyDeviceToHost, s_));
+      if (K > 0) {
+        launch_logits_topk(m.mb.logits.as<float>(), m.V, m.ctl.as<LogitsCtl>(), m.vids, R, K, m.work.as<float>(),
+                           m.beamc.as<BeamCand>(), s_);
+        WDR_HIP(wdr_memcpy_async(m.h_beam, m.beamc.p, (size_t)R * K * sizeof(BeamCand), hipMemcpyDeviceToHost, s_));
+      }
+    });
     g.vids = m.vids;
   } else {
     tb.upload(io, s_, false, false);   // the captured copy node reads the staging
   }
-  {
-    std::mutex* mu = launch_lock();   // WDR_LAUNCH_LOCK (prof.h)
-    if (mu) mu->lock();
-    const hipError_t ge = hipGraphLaunch(g.exec, s_);
-    if (mu) mu->unlock();
-    WDR_HIP(ge);
-  }
+  replay(g.exec, s_);
   WDR_HIP(hipStreamSynchronize(s_));
   if (K > 0) memcpy(cands, m.h_beam, (size_t)R * K * sizeof(BeamCand));
-  for (int r = 0; r < R; ++r) {
-    const TokOut& o = m.h_tok[r];
-    TokenData t;
-    t.id = o.id;
-    t.tid = o.tid;
-    t.p = o.p;
-    t.plog = o.plog;
-    t.pt = o.pt;
-    t.ptsum = o.ptsum;
-    out[r] = t;
-  }
+  for (int r = 0; r < R; ++r) out[r] = token_data(m.h_tok[r]);
   times.decode_steps++;
 }
 
@@ -1887,16 +1603,8 @@ void State::run_logits(int R, const LogitsCtl* ctl, TokenData* out, float* nosp)
   WDR_HIP(wdr_memcpy_async(m.h_tok, m.tokout.p, R * sizeof(TokOut), hipMemcpyDeviceToHost, s_));
   WDR_HIP(hipStreamSynchronize(s_));
   for (int r = 0; r < R; ++r) {
-    const TokOut& o = m.h_tok[r];
-    TokenData t;
-    t.id = o.id;
-    t.tid = o.tid;
-    t.p = o.p;
-    t.plog = o.plog;
-    t.pt = o.pt;
-    t.ptsum = o.ptsum;
-    out[r] = t;
-    if (nosp) nosp[r] = o.nosp_prob;
+    out[r] = token_data(m.h_tok[r]);
+    if (nosp) nosp[r] = m.h_tok[r].nosp_prob;
   }
 }
 
@@ -2830,7 +2538,7 @@ int State::full(const FullParams& params, const float* samples, int n, int job, 
   // WDR_CHAIN_LOG=<file>: one line per full() call -- chain, job, wall at entry and exit (s), top_up ms,
   // ready-wait ms, energy ms, decode ms (windows' decode loops), post ms (results, heuristic
   // timestamps, DTW submit) -- where a chain spends the time between its batched steps
-  static FILE* clog = getenv("WDR_CHAIN_LOG") ? fopen(getenv("WDR_CHAIN_LOG"), "w") : nullptr;
+  static FILE* clog = env_set("WDR_CHAIN_LOG") ? fopen(env_str("WDR_CHAIN_LOG"), "w") : nullptr;
   static std::mutex clog_mu;
   double c_top = 0, c_ready = 0, c_energy = 0, c_dec = 0, c_post = 0;
   const double c_t0 = now_s();
@@ -3032,7 +2740,7 @@ int State::full(const FullParams& params, const float* samples, int n, int job, 
       // multi-chain beam search at t = 0: its prompt prefill rides in a batched step too, with the
       // prompt's top-K candidates (decode_beam)
       // (WDR_BEAM_PREFILL=0: on the chain's own stream as before, A/B; read once)
-      static const bool beam_pre_on = !(getenv("WDR_BEAM_PREFILL") && atoi(getenv("WDR_BEAM_PREFILL")) == 0);
+      static const bool beam_pre_on = env_on("WDR_BEAM_PREFILL", true);
       const bool beam_pre = beam_pre_on && batched && !params.greedy && t_cur <= 0.f;
       if (!pre_batched && !beam_pre) {
         flush_dtw();
@@ -3266,7 +2974,7 @@ struct StepBatcher::Impl {
   // once the GPU is free (default 1000 us: at 40 chains 300 / 600 / 1000 us gave 744 / 755 / 758
   // xRT, profiles/r04/ab_wait40.txt; negative: wait for every chain, the round-3 rule)
   double wait_s = 1000e-6;
-  hipStream_t s = nullptr;
+  StreamRef s;
   int d = 0, V = 0, H = 0;
   int RB = 0, LB = 0;             // row / logit-row capacity of one launch
   RowsBufs bufs;
@@ -3295,10 +3003,8 @@ StepBatcher::StepBatcher(Context& ctx) : ctx_(ctx), m_(new Impl) {
   m.d = hp.n_text_state;
   m.V = hp.n_vocab;
   m.H = hp.n_text_head;
-  int lo = 0, hi = 0;
-  WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  m.s = dedicated_stream("WDR_BATCH_HWQ", false, hi);
-  if (const char* e = getenv("WDR_BATCH_WAIT_US")) m.wait_s = atof(e) * 1e-6;
+  m.s = open_stream(StreamRole::StepBatcher, stream_knobs_env());   // read per batcher
+  if (env_set("WDR_BATCH_WAIT_US")) m.wait_s = env_double("WDR_BATCH_WAIT_US", 0) * 1e-6;
   const int RB = rows_cap(ctx), LB = logit_cap(ctx);
   m.RB = RB;
   m.LB = LB;
@@ -3320,10 +3026,7 @@ StepBatcher::~StepBatcher() {
   if (!m_) return;
   if (m_->s) (void)hipStreamSynchronize(m_->s);
   for (auto& g : m_->graphs) g.second.drop();
-  if (m_->s) {
-    (void)hipStreamSynchronize(m_->s);
-    (void)hipStreamDestroy(m_->s);
-  }
+  close_stream(m_->s);
   (void)hipHostFree(m_->h_ctl);
   (void)hipHostFree(m_->h_tok);
   (void)hipHostFree(m_->h_beam);
@@ -3514,7 +3217,7 @@ void StepBatcher::launch(std::vector<Req*>& batch) {
   // only a batch that would replay a graph draws an eager sampled run (prof.h): mixed batches
   // always run eagerly and are sampled at the base rate
   const bool sampled = decode_only && !no_graph() && prof_step();
-  static FILE* blog = getenv("WDR_BATCH_LOG") ? fopen(getenv("WDR_BATCH_LOG"), "w") : nullptr;
+  static FILE* blog = env_set("WDR_BATCH_LOG") ? fopen(env_str("WDR_BATCH_LOG"), "w") : nullptr;
   if (blog) WDR_HIP(hipEventRecord(m.ev0, m.s));
   if (sampled || no_graph() || !decode_only) {
     // sampled step for live kernel timing (prof.h: its launches run eagerly, 1 in 2 of them
@@ -3535,43 +3238,21 @@ void StepBatcher::launch(std::vector<Req*>& batch) {
     Impl::G& g = m.graphs[((long long)K << 40) + (grouped ? 1ll << 39 : 0ll) + ((long long)tb.n_vgrp << 16) + R];
     if (g.exec && memcmp(&g.vids, &vids, sizeof(VocabIds)) != 0) g.drop();
     if (!g.exec) {
-      std::lock_guard<std::recursive_mutex> cap_lock(hip_alloc_mutex());   // no allocation meanwhile
-      hipGraph_t graph;
-      prof_capture(true);
-      WDR_HIP(hipStreamBeginCapture(m.s, hipStreamCaptureModeRelaxed));
-      tb.upload(io, m.s, true, false);
-      rows_forward(ctx_, io, R, m.s);
-      tail();
-      prof_capture(false);
-      WDR_HIP(hipStreamEndCapture(m.s, &graph));
-      WDR_HIP(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-      WDR_HIP(hipGraphDestroy(graph));
+      g.exec = capture_exec(m.s, [&] {
+        tb.upload(io, m.s, true, false);
+        rows_forward(ctx_, io, R, m.s);
+        tail();
+      });
       g.vids = vids;
     } else {
       tb.upload(io, m.s, false, false);   // the captured copy node reads the staging
     }
-    {
-      std::mutex* mu = launch_lock();   // WDR_LAUNCH_LOCK (prof.h)
-      if (mu) mu->lock();
-      const hipError_t ge = hipGraphLaunch(g.exec, m.s);
-      if (mu) mu->unlock();
-      WDR_HIP(ge);
-    }
+    replay(g.exec, m.s);
   }
   if (blog) WDR_HIP(hipEventRecord(m.ev1, m.s));
   const double t_enq = now_s();   // host side of the launch done (eager: every kernel enqueued)
   WDR_HIP(hipStreamSynchronize(m.s));
-  auto tok_of = [&](int i) {
-    const TokOut& o = m.h_tok[i];
-    TokenData t{};
-    t.id = o.id;
-    t.tid = o.tid;
-    t.p = o.p;
-    t.plog = o.plog;
-    t.pt = o.pt;
-    t.ptsum = o.ptsum;
-    return t;
-  };
+  auto tok_of = [&](int i) { return token_data(m.h_tok[i]); };
   for (size_t i = 0; i < batch.size(); ++i) {
     Req* q = batch[i];
     if (lidx[i] >= 0)
@@ -3626,7 +3307,7 @@ struct DtwQueue::Impl {
   bool stop = false;
   std::exception_ptr err;
   std::thread th;
-  hipStream_t s = nullptr;
+  StreamRef s;
   int RB = 0, A = 1, l_end = 1, min_rows = 256;
   double max_age = 0.05;
   RowsBufs bufs;
@@ -3648,11 +3329,9 @@ DtwQueue::DtwQueue(Context& ctx) : m_(new Impl), ctx_(ctx) {
   m.A = std::max<int>(1, (int)ctx.aheads.size());
   m.l_end = capture_l_end(ctx);
   m.RB = 1024;   // rows of one pass (a DTW re-forward is <= RMAX + 1 rows)
-  if (const char* e = getenv("WDR_DTW_MIN_ROWS")) m.min_rows = std::max(1, atoi(e));
-  if (const char* e = getenv("WDR_DTW_AGE_MS")) m.max_age = std::max(0.0, atof(e)) * 1e-3;
-  int lo = 0, hi = 0;
-  WDR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  m.s = dedicated_stream("WDR_DTWQ_HWQ", false, lo);
+  if (env_set("WDR_DTW_MIN_ROWS")) m.min_rows = std::max(1, env_int("WDR_DTW_MIN_ROWS", 0));
+  if (env_set("WDR_DTW_AGE_MS")) m.max_age = std::max(0.0, env_double("WDR_DTW_AGE_MS", 0)) * 1e-3;
+  m.s = open_stream(StreamRole::DtwQueue, stream_knobs_env());   // read per queue
   m.bufs.alloc(m.RB, 1, hp.n_text_state, hp.n_text_head, hp.n_vocab);
   m.tb = std::make_unique<RowBatch>(m.RB, 1, m.RB);
   m.cap = DevMem((size_t)m.A * m.RB * 1500 * 4);
@@ -3672,10 +3351,7 @@ DtwQueue::~DtwQueue() {
   }
   m_->cv.notify_all();
   if (m_->th.joinable()) m_->th.join();
-  if (m_->s) {
-    (void)hipStreamSynchronize(m_->s);
-    (void)hipStreamDestroy(m_->s);
-  }
+  close_stream(m_->s);
 }
 
 void DtwQueue::submit(const std::shared_ptr<DtwQJob>& j) {

@@ -104,6 +104,13 @@ class ResultSeg(C.Structure):
 
 
 P = C.POINTER
+
+
+class StreamPlan(C.Structure):
+    _fields_ = [("kind", i32), ("prio", i32), ("pool", i32), ("n_words", i32), ("mask", C.c_uint32 * 16),
+                ("tag", C.c_char * 32)]
+
+
 _SIGS = {
     "wdr_last_error": (cstr, []),
     "wdr_abi_version": (C.c_int, []),
@@ -161,6 +168,8 @@ _SIGS = {
     "wdr_dbg_set_early_fixup": (C.c_int, [vp, i32]),
     "wdr_dbg_set_gemm32": (C.c_int, [i32]),
     "wdr_dbg_gemm_plan": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, P(i32), P(i32)]),
+    "wdr_dbg_cu_mask": (C.c_int, [i32, i32, i32, i32, P(C.c_uint32), i32]),
+    "wdr_dbg_stream_plan": (C.c_int, [i32, i32, P(i32), P(StreamPlan)]),
     "wdr_ggml_info": (C.c_int, [cstr, P(i32), P(i64), P(i64)]),
     "wdr_ggml_tensor_types": (C.c_int, [cstr, P(i64)]),
     "wdr_ggml_tensor_f16": (C.c_int, [cstr, cstr, P(P(C.c_uint16)), P(sz)]),
