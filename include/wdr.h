@@ -27,6 +27,9 @@
  *   wdr_read_audio_channels              any supported WAV -> 16 kHz int16 per channel (planar), on the GPU
  *   wdr_engine_set_channel_split         wdr_transcribe_audio transcribes every channel on its own,
  *                                        speaker = channel
+ *   wdr_transcribe_batch / wdr_batch_free many files in one call, each equal to its wdr_transcribe_audio
+ *   wdr_run_pipeline_groups              several recordings' segments in one pipeline run (segment groups)
+ *   wdr_vad_probs_batch                  wdr_vad_probs of several recordings in one pass
  * The wdr_dbg_* functions are kernel-level test seams (parity tests call them).
  */
 #ifndef WDR_H
@@ -223,6 +226,38 @@ int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on);
 int wdr_engine_set_channel_split(wdr_engine* e, int8_t on);
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* opts,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out);
+/* Batch transcription (additive, not in the Rust API): n_files recordings in one call, so that
+ * short files share the decode chains and the VAD scans run side by side.  (*out)[i].list equals
+ * what wdr_transcribe_audio(e, audio_paths[i], opts, fmt, ..) returns on the same engine (segments,
+ * words, times, speaker ids, detected_lang) in every engine mode (read_wav, audio convert, channel
+ * split; with and without enable_vad): every file -- every channel under channel split -- is one
+ * segment group of a single wdr_run_pipeline_groups call.
+ * A file that cannot be read gets (*out)[i].error = the message the single call gives
+ * ("audio file doesn't exist", the header errors, ..) and list == NULL; the other files are
+ * unaffected.  Model not found, translate_target, cancellation and GPU errors fail the whole call
+ * as they fail wdr_transcribe_audio.  enable_diarize == 1 fails before any file is read: "batch
+ * transcription does not diarize: enable_diarize must not be set".  n_files == 0 succeeds with
+ * *out == NULL.  new_segment fires in (file, channel, segment) order on the calling thread with
+ * the file's index; progress reports finished speech segments over all files.
+ * Free *out with wdr_batch_free. */
+typedef struct {
+  wdr_segment_list* list;                 /* exactly one of list / error is non-NULL */
+  const char* error;
+} wdr_batch_item;
+typedef struct {
+  void* user;
+  void (*progress)(void* user, int32_t pct, int32_t type, const char* label);
+  void (*new_segment)(void* user, size_t file_index, const wdr_segment* seg);
+  int (*is_cancelled)(void* user);
+} wdr_batch_callbacks;
+int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n_files,
+                         const wdr_transcribe_options* opts, const wdr_formatting_overrides* fmt,
+                         const wdr_batch_callbacks* cb, wdr_batch_item** out /* [n_files] */);
+void wdr_batch_free(wdr_batch_item* items, size_t n_files);
+/* stage accounting of the engine's context of `model` (NULL = "base"), as wdr_context_stage_times
+ * reports a context's; an error before the engine's first call with that model.
+ * wdr_transcribe_batch starts the multi-chain figures (chains, batch_*, fixup_*) afresh */
+int wdr_engine_stage_times(wdr_engine* e, const char* model, wdr_stage_times* out);
 
 /* ---- seams ---- */
 int wdr_read_wav(const char* path, int16_t** samples, size_t* n);
@@ -267,6 +302,11 @@ void wdr_vad_free(wdr_vad* v);
 /* one probability per 512-sample chunk: probs_out[ceil(n/512)]; us_per_step (nullable) = GPU
  * time of the forward per chunk (the LSTM scan dominates) */
 int wdr_vad_probs(wdr_vad* v, const int16_t* samples, size_t n, float* probs_out, double* us_per_step);
+/* B independent sequences in one pass (one upload, three launches, one sync; the LSTM scans run
+ * one workgroup per sequence): probs_out holds ceil(n[b] / 512) values per sequence, back to back,
+ * bit-identical to wdr_vad_probs of each.  n[b] == 0 is legal (samples[b] is not read) */
+int wdr_vad_probs_batch(wdr_vad* v, const int16_t* const* samples, const size_t* n, int32_t B,
+                        float* probs_out, double* us_per_step);
 /* GPU time of the last forward per 512-sample chunk (microseconds) */
 int wdr_vad_stats(wdr_vad* v, double* us_per_chunk);
 /* whisper.cpp whisper_vad_segments_from_probs with the reference's params (min silence 100 ms):
@@ -351,6 +391,22 @@ int wdr_run_pipeline_raw(wdr_context* c, const wdr_speech_segment* segs, size_t 
 int wdr_run_pipeline_block(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
                            const wdr_transcribe_options* opts, const wdr_synthetic* syn, const char* rng_in,
                            int8_t* sampled_out, char** rng_out, wdr_segment_list** out);
+/* Segment groups: group g is segs[group_start[g] .. group_start[g + 1]) (the last one ends at
+ * n_segs) and comes out, as out[g], exactly as if it had been the whole input of its own
+ * wdr_run_pipeline call without diarization -- prompt chain, decoder 0's random numbers, overlap
+ * clip, detected language and speech_index all start afresh at a group start -- while the decode
+ * chains are shared by all groups.  group_start is non-decreasing with
+ * group_start[0] == 0 and every entry <= n_segs (else an error before any GPU work); an empty
+ * group yields an empty list.  group_speaker (nullable, entries nullable): a fixed speaker_id for
+ * group g's segments.  new_segment fires in (group, segment) order on the calling thread;
+ * progress counts finished segments over all of them.  out: n_groups lists, each freed with
+ * wdr_segment_list_free.  n_groups == 0 needs n_segs == 0 and does nothing.  Speaker embeddings
+ * are per pipeline call, so more than one group with opts->enable_diarize == 1 is refused:
+ * "segment groups do not diarize: more than one group with diarization on". */
+int wdr_run_pipeline_groups(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
+                            const size_t* group_start, size_t n_groups, const char* const* group_speaker,
+                            const wdr_transcribe_options* opts, const wdr_synthetic* syn,
+                            const wdr_callbacks* cb, wdr_segment_list** out /* [n_groups] */);
 void wdr_segment_list_free(wdr_segment_list* l);
 /* decode chains of run_pipeline (greedy decoding): n States decode n contiguous blocks of the
  * speech segments concurrently, their greedy steps batched into one n-row step, with an exact

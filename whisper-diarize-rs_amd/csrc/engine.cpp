@@ -388,9 +388,8 @@ struct wdr_engine {
 
 // src/vad.rs:6-85 on top of the GPU VAD: probabilities -> whisper.cpp segments (cs) -> the
 // crate's own merge/slice (same code as wdr_vad_merge).  Segments borrow `pcm`.
-static void vad_get_segments(VadModel& vm, const int16_t* pcm, size_t n, std::vector<std::pair<double, double>>* mask,
-                             std::vector<wdr_speech_segment>* segs) {
-  const std::vector<float> pr = vm.probs(pcm, n);
+static void vad_segments_of(const std::vector<float>& pr, const int16_t* pcm, size_t n,
+                            std::vector<std::pair<double, double>>* mask, std::vector<wdr_speech_segment>* segs) {
   const std::vector<std::pair<float, float>> cs = vad_segments_from_probs(pr, VadParams());
   mask->clear();
   for (auto& c : cs) {
@@ -411,6 +410,10 @@ static void vad_get_segments(VadModel& vm, const int16_t* pcm, size_t n, std::ve
     if (!(m.second > m.first) || !(ei > si)) continue;
     segs->push_back({m.first, m.second, pcm + si, ei - si});
   }
+}
+static void vad_get_segments(VadModel& vm, const int16_t* pcm, size_t n, std::vector<std::pair<double, double>>* mask,
+                             std::vector<wdr_speech_segment>* segs) {
+  vad_segments_of(vm.probs(pcm, n), pcm, n, mask, segs);
 }
 
 // src/transcribe.rs:20-87
@@ -698,10 +701,18 @@ static std::vector<float> seg_f32(const wdr_speech_segment& s) {
 // state.  The output equals the single-chain loop's exactly.
 // rng0: decoder 0's RNG entering the first segment (the fresh state's, or the state a previous
 // block of the same file left, multi-GPU one-file path); "clean" below means "equal to rng0".
+// Segment groups: gs[0 .. n_groups] are group boundaries, gs.back() == N.  A group
+// is decoded as if it were a pipeline call of its own, so at a group's first segment the prompt
+// is e0 again and decoder 0's RNG is rng0 again, wherever the blocks are cut; "earlier" and "the
+// rest of the file" above then read "earlier in the group" and "the rest of the group".
 static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_speech_segment>& segs,
-                                         const wdr_transcribe_options* o, const FullParams& params, int C,
-                                         const wdr_callbacks* cb, const std::string& rng0) {
+                                         const std::vector<size_t>& gs, const wdr_transcribe_options* o,
+                                         const FullParams& params, int C, const wdr_callbacks* cb,
+                                         const std::string& rng0) {
   const size_t N = segs.size();
+  std::vector<char> gstart(N, 0);   // a group starts at segment i
+  for (size_t g = 0; g + 1 < gs.size(); ++g)
+    if (gs[g] < N) gstart[gs[g]] = 1;
   const int G = (int)c->devices.size();
   // chain k: GPU k % G, chain k / G of that GPU's KV pool (a fixed mapping, so states persist)
   auto ctx_of = [&](int k) -> Context& { return k % G == 0 ? *c->ctx : *c->peers[k % G - 1]; };
@@ -788,6 +799,7 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
       ~Hint() { st.lang_hint = -1; }
     } hint{st};
     for (size_t j = a; j < b && !stop; ++j) {
+      if (gstart[j]) e = e0;   // a group's first segment never sees the group before it
       const std::vector<float> x = seg_f32(segs[j]);
       st.set_rng_state(rng0);
       // the speculative pass detected this segment's language from its window 0 alone: the
@@ -877,6 +889,11 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
       } resolve_guard{st, tks, out};
       bool drew = false;   // a segment of this block drew before: decoder 0's RNG is no longer initial
       for (size_t i = a; i < b && !stop; ++i) {
+        if (i > a && gstart[i]) {   // a new group inside the block: as at a block's start
+          e = e0;
+          st.set_rng_state(rng0);
+          drew = false;
+        }
         if (st.full(with_prompt(params, e), nullptr, 0, (int)(i - a), true) != 0)
           throw std::runtime_error("failed to transcribe");
         out[i].res = st.result_all;
@@ -911,11 +928,13 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
     try {
       static const int env_mode = env_int("WDR_EARLY_FIXUP", 3);
       const int mode = c->early_fixup >= 0 ? c->early_fixup : env_mode;
-      if (mode == 2 && k > 0)
+      // a block that starts a group was decoded from its true prompt, e0: nothing to wait for or redo
+      const bool dep = k > 0 && !gstart[cut[k]];
+      if (mode == 2 && dep)
         while (!done[k - 1].load() && !stop) std::this_thread::sleep_for(std::chrono::microseconds(200));
-      if (mode == 3 && k > 0)
+      if (mode == 3 && dep)
         while (!spec_done[k - 1].load() && !stop) std::this_thread::sleep_for(std::chrono::microseconds(200));
-      if (mode > 0 && !errs[k] && !stop && k > 0 && (mode == 3 ? spec_done[k - 1].load() : done[k - 1].load())) {
+      if (mode > 0 && !errs[k] && !stop && dep && (mode == 3 ? spec_done[k - 1].load() : done[k - 1].load())) {
         Prompt et;
         if (done[k - 1].load()) {
           et = spec_out[cut[k] - 1];   // the predecessor finished: its block no longer changes
@@ -968,7 +987,7 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
     std::vector<int> redo;
     std::vector<Prompt> e_true(C);
     for (int k = 1; k < C; ++k) {
-      e_true[k] = spec_out[cut[k] - 1];
+      e_true[k] = gstart[cut[k]] ? e0 : spec_out[cut[k] - 1];
       if (e_true[k] != dec_in[k]) redo.push_back(k);
     }
     if (redo.empty()) break;
@@ -1006,21 +1025,24 @@ static std::vector<SegOut> decode_chains(wdr_context* c, const std::vector<wdr_s
   // that state it is exact and the re-decode starts after it (from its RNG state); if not (a
   // speculative segment before it in its block drew, and the fix-up stopped before redoing it),
   // the re-decode starts at it, from the initial state.  Every later segment is re-decoded in order.
-  size_t f = N;
-  for (size_t i = 0; i < N; ++i)
-    if (out[i].sampled) {
-      f = i;
-      break;
-    }
-  const size_t rs = (f < N && !out[f].rng_clean) ? f : f + 1;
-  if (rs < N) {
+  // Per group: a group's draws start from the initial state and end with the group.
+  for (size_t g = 0; g + 1 < gs.size(); ++g) {
+    const size_t ga = gs[g], gb = gs[g + 1];
+    size_t f = gb;
+    for (size_t i = ga; i < gb; ++i)
+      if (out[i].sampled) {
+        f = i;
+        break;
+      }
+    const size_t rs = (f < gb && !out[f].rng_clean) ? f : f + 1;
+    if (rs >= gb) continue;
     on_gpu(0);
     State& st = *c->st;
     Prompt e = e0;
-    for (size_t i = 0; i < rs; ++i) e = next_prompt(e, out[i].res);
+    for (size_t i = ga; i < rs; ++i) e = next_prompt(e, out[i].res);
     if (rs == f) st.set_rng_state(rng0);
     else st.set_rng_state(out[f].rng_after);
-    for (size_t i = rs; i < N; ++i) {
+    for (size_t i = rs; i < gb; ++i) {
       if (cb && cb->is_cancelled && cb->is_cancelled(cb->user)) throw std::runtime_error("failed to transcribe");
       const std::vector<float> x = seg_f32(segs[i]);
       c->cs.replays++;
@@ -1074,11 +1096,28 @@ struct RngCarry {
   std::string rng_out;
   std::vector<char> sampled;
 };
-static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speech_segment>& segs,
-                                     const wdr_transcribe_options* o, const wdr_diarize_options* dopts,
-                                     const SynCfg& syn, const wdr_callbacks* cb, std::string* detected_lang,
-                                     bool* has_lang, bool raw = false, RngCarry* carry = nullptr,
-                                     const char* fixed_speaker = nullptr) {
+// Segment groups: gs[0 .. G] are group boundaries (gs[0] == 0, gs[G] == segs.size(),
+// non-decreasing).  Group g comes out as if segs[gs[g] .. gs[g + 1]) had been a call of its own:
+// the prompt chain, decoder 0's RNG, the overlap clip, the detected language and the speech index
+// restart at its first segment, while all groups share the decode chains.  One group is the
+// reference's pipeline.  group_speaker (nullable, entries nullable): a fixed speaker label per group.
+struct GroupLang {
+  std::string lang;
+  bool has = false;
+};
+static std::vector<std::vector<Seg>> run_pipeline_groups(
+    wdr_context* c, const std::vector<wdr_speech_segment>& segs, const std::vector<size_t>& gs,
+    const wdr_transcribe_options* o, const wdr_diarize_options* dopts, const SynCfg& syn, const wdr_callbacks* cb,
+    std::vector<GroupLang>* langs, bool raw = false, RngCarry* carry = nullptr,
+    const std::vector<const char*>* group_speaker = nullptr, size_t* cur_group = nullptr) {
+  // cur_group (nullable): set to a segment's group before its new_segment callback fires
+  const size_t n_groups = gs.size() - 1;
+  if (dopts && n_groups > 1)
+    throw std::runtime_error("segment groups do not diarize: more than one group with diarization on");
+  if (carry && n_groups > 1) throw std::runtime_error("segment groups: the RNG carry is single-group");
+  std::vector<size_t> grp(segs.size(), 0);   // group of segment i
+  for (size_t g = 0; g < n_groups; ++g)
+    for (size_t i = gs[g]; i < gs[g + 1]; ++i) grp[i] = g;
   const bool diarize = dopts != nullptr && !raw;
   const float dthr = dopts ? dopts->threshold : 0.5f;
   SpeakerManager speakers(dopts ? dopts->max_speakers : UINT64_MAX);
@@ -1122,14 +1161,15 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
   FullParams params = setup_params(o, syn);
   const Vocab& v = c->ctx->vocab;
   const double user_offset = (o && o->has_offset) ? o->offset : 0.0;
-  std::vector<Seg> out;
+  std::vector<std::vector<Seg>> outs(n_groups);
   bool have_prev = false;
   std::string previous_text;
-  *has_lang = false;
-  if (o && o->lang && std::string(o->lang) != "auto") {
-    *detected_lang = o->lang;
-    *has_lang = true;
-  }
+  const bool prompt0_has = params.has_initial_prompt;   // the prompt entering a group's first segment
+  const std::string prompt0 = params.initial_prompt;
+  langs->assign(n_groups, GroupLang{});
+  if (o && o->lang && std::string(o->lang) != "auto")
+    for (GroupLang& l : *langs) l = {o->lang, true};
+  if (n_groups == 0) return outs;
   const bool translated = o && o->whisper_to_english == 1;
   // decode chains: greedy and beam search at t = 0 (their steps batch across chains; t > 0
   // decoders from the first window on keep one chain)
@@ -1194,6 +1234,8 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
     P.tk.clear();
     const size_t i = P.i;
     const wdr_speech_segment& ss = segs[i];
+    std::vector<Seg>& out = outs[grp[i]];   // the overlap clip below never reaches into another group
+    const char* fixed_speaker = group_speaker ? (*group_speaker)[grp[i]] : nullptr;
     const double base_offset = ss.start + user_offset;
     const float* emb = nullptr;
     bool have_emb = false;
@@ -1224,7 +1266,7 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
       s.text = text;
       s.has_words = !words.empty();
       s.words = std::move(words);
-      s.src = (int64_t)i;
+      s.src = (int64_t)(i - gs[grp[i]]);
       if (diarize) {
         // src/transcribe.rs:461-497: embed the whole speech segment (recomputed per whisper
         // segment in the reference; identical input -> computed once here), then assign
@@ -1240,6 +1282,7 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
         s.has_speaker = true;
         s.speaker = fixed_speaker;
       }
+      if (cur_group) *cur_group = grp[i];
       emit_segment(cb, s);
       if (cb && cb->progress) {
         const int pct = (int)((double)(i + 1) / (double)segs.size() * 100.0);
@@ -1251,7 +1294,7 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
   if (C > 1) {
     // multi-chain: C States decode C contiguous blocks concurrently (batched greedy steps),
     // then the exact prompt fix-up; results come back DTW-resolved, finished here in order
-    std::vector<SegOut> res = decode_chains(c, segs, o, params, C, cb, rng0);
+    std::vector<SegOut> res = decode_chains(c, segs, gs, o, params, C, cb, rng0);
     if (carry) {
       carry->rng_out = rng0;
       for (size_t i = 0; i < segs.size(); ++i) {
@@ -1260,18 +1303,22 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
       }
     }
     for (size_t i = 0; i < segs.size(); ++i) {
-      if (i == 0 && !*has_lang) {
-        *detected_lang = kLangs[std::max(0, std::min(99, res[0].lang_id))];
-        *has_lang = true;
-      }
+      GroupLang& gl = (*langs)[grp[i]];
+      if (i == gs[grp[i]] && !gl.has) gl = {kLangs[std::max(0, std::min(99, res[i].lang_id))], true};
       Pending P;
       P.i = i;
       P.res = std::move(res[i].res);
       finalize(P);
     }
-    return out;
+    return outs;
   }
   for (size_t i = 0; i < segs.size(); ++i) {
+    if (i > 0 && i == gs[grp[i]]) {   // a new group: the initial prompt and a fresh state's RNG
+      have_prev = false;
+      params.has_initial_prompt = prompt0_has;
+      params.initial_prompt = prompt0;
+      c->st->reset_rng();
+    }
     if (have_prev) {
       params.initial_prompt = previous_text;
       params.has_initial_prompt = true;
@@ -1285,10 +1332,8 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
     }
     if (rc != 0) throw std::runtime_error("failed to transcribe");
     if (carry) carry->sampled[i] = c->st->sampled;
-    if (!*has_lang) {
-      *detected_lang = kLangs[std::max(0, std::min(99, c->st->lang_id))];
-      *has_lang = true;
-    }
+    GroupLang& gl = (*langs)[grp[i]];   // the group's first segment decides
+    if (!gl.has) gl = {kLangs[std::max(0, std::min(99, c->st->lang_id))], true};
     Pending cur;
     cur.i = i;
     cur.res = c->st->result_all;
@@ -1309,7 +1354,38 @@ static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speec
     pend.clear();
   }
   if (carry) carry->rng_out = c->st->rng_state();
-  return out;
+  return outs;
+}
+
+static std::vector<Seg> run_pipeline(wdr_context* c, const std::vector<wdr_speech_segment>& segs,
+                                     const wdr_transcribe_options* o, const wdr_diarize_options* dopts,
+                                     const SynCfg& syn, const wdr_callbacks* cb, std::string* detected_lang,
+                                     bool* has_lang, bool raw = false, RngCarry* carry = nullptr,
+                                     const char* fixed_speaker = nullptr) {
+  std::vector<GroupLang> langs;
+  const std::vector<const char*> spk{fixed_speaker};
+  std::vector<std::vector<Seg>> outs =
+      run_pipeline_groups(c, segs, {0, segs.size()}, o, dopts, syn, cb, &langs, raw, carry, &spk);
+  *detected_lang = langs[0].lang;
+  *has_lang = langs[0].has;
+  return std::move(outs[0]);
+}
+
+// group_start as the ABI takes it -> boundaries gs[0 .. n_groups] with gs[n_groups] == n_segs
+static std::vector<size_t> group_bounds(const size_t* group_start, size_t n_groups, size_t n_segs) {
+  if (n_groups == 0) {
+    if (n_segs != 0) throw std::runtime_error("segment groups: segments without a group");
+    return {0};
+  }
+  if (!group_start) throw std::runtime_error("segment groups: group_start is NULL");
+  if (group_start[0] != 0) throw std::runtime_error("segment groups: group_start[0] must be 0");
+  std::vector<size_t> gs(group_start, group_start + n_groups);
+  gs.push_back(n_segs);
+  for (size_t g = 0; g < n_groups; ++g) {
+    if (gs[g] > n_segs) throw std::runtime_error("segment groups: group_start past the last segment");
+    if (gs[g] > gs[g + 1]) throw std::runtime_error("segment groups: group_start must not decrease");
+  }
+  return gs;
 }
 
 // ------------------------------------------------------------------ read_wav (src/audio.rs:4-24)
@@ -1707,6 +1783,228 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
   })
 }
 
+// DESIGN.md §3e.  The order of work: read (and convert) every file; one batched VAD pass over all
+// files' channels; one grouped pipeline run, a group per file (per channel under channel split);
+// process_segments per file / channel with its own mask and language preset -- each step what
+// wdr_transcribe_audio does for one file, so the lists are equal to its lists.
+int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n_files,
+                         const wdr_transcribe_options* o, const wdr_formatting_overrides* fmt,
+                         const wdr_batch_callbacks* cb, wdr_batch_item** out) {
+  WDR_GUARD({
+    WDR_USE(eng, e);
+    if (!out) return fail("batch transcription: out is NULL");
+    *out = nullptr;
+    if (o && o->enable_diarize == 1)
+      return fail("batch transcription does not diarize: enable_diarize must not be set");
+    if (n_files == 0) return 0;
+    if (!audio_paths) return fail("batch transcription: audio_paths is NULL");
+    const std::string model = (o && o->model) ? o->model : "base";
+    auto it = e->contexts.find(model);
+    std::string model_path;
+    if (it == e->contexts.end()) {
+      model_path = find_model_file(e->cache_dir, model);
+      if (model_path.empty() && !e->syn_set) return fail("whisper file doesn't exist");
+    }
+    if (o && o->translate_target && !(o->whisper_to_english == 1))
+      return fail("translate_target: network translation is out of scope for libwdr");
+    const bool vad = !o || o->enable_vad == 1;
+    const int dev = e->cfg.has_gpu_device ? e->cfg.gpu_device : 0;
+    struct File {
+      std::string err;
+      bool ok = false;
+      int n_ch = 1;
+      std::vector<int16_t> pcm;   // planar [n_ch][n]
+      size_t n = 0, seq0 = 0;     // samples per channel; index of channel 0's sequence
+    };
+    struct Seq {   // one channel of one file: a mono recording of its own
+      size_t file = 0;
+      int ch = 0;
+      const int16_t* x = nullptr;
+      size_t n = 0;
+      std::vector<std::pair<double, double>> mask;
+      std::vector<wdr_speech_segment> segs;
+      long long group = -1;   // its segment group; -1: no pipeline run (channel split, no speech)
+      std::string label;      // channel split: the speaker
+    };
+    std::vector<File> files(n_files);
+    std::vector<Seq> seqs;
+    for (size_t i = 0; i < n_files; ++i) {
+      File& f = files[i];
+      if (cb && cb->is_cancelled && cb->is_cancelled(cb->user)) return fail("failed to transcribe");
+      if (!audio_paths[i] || !file_exists(audio_paths[i])) {
+        f.err = "audio file doesn't exist";
+        continue;
+      }
+      try {
+        f.pcm = e->channel_split   ? read_audio_file_channels(audio_paths[i], dev, &e->conv, &f.n_ch)
+                : e->audio_convert ? read_audio_file(audio_paths[i], dev, &e->conv)
+                                   : read_wav_impl(audio_paths[i]);
+      } catch (const HipError&) {
+        throw;   // the GPU, not the file
+      } catch (const std::exception& ex) {
+        f.err = ex.what();
+        continue;
+      }
+      f.ok = true;
+      f.n = f.pcm.size() / (size_t)f.n_ch;
+      f.seq0 = seqs.size();
+      for (int c = 0; c < f.n_ch; ++c) {
+        Seq s;
+        s.file = i;
+        s.ch = c;
+        s.x = f.pcm.data() + (size_t)c * f.n;
+        s.n = f.n;
+        s.label = std::to_string(c + 1);
+        seqs.push_back(std::move(s));
+      }
+    }
+    if (vad && !seqs.empty()) {
+      std::string vp;
+      if (!e->vad_path.empty()) {
+        if (!file_exists(e->vad_path.c_str())) return fail("VAD model file doesn't exist: " + e->vad_path);
+        vp = e->vad_path;
+      } else {
+        vp = find_cached_file(e->cache_dir, "models--ggml-org--whisper-vad", "ggml-silero-v5.1.2.bin");
+        if (vp.empty() && !e->syn_set) return fail("VAD model file doesn't exist");
+      }
+      if (!e->vad || e->vad_loaded != vp) {
+        e->vad.reset();
+        e->vad = std::make_unique<VadModel>(dev, vp);
+        e->vad_loaded = vp;
+      }
+      std::vector<const int16_t*> px(seqs.size());
+      std::vector<size_t> pn(seqs.size());
+      for (size_t s = 0; s < seqs.size(); ++s) {
+        px[s] = seqs[s].x;
+        pn[s] = seqs[s].n;
+      }
+      const std::vector<std::vector<float>> pr = e->vad->probs_batch(px.data(), pn.data(), (int)seqs.size());
+      for (size_t s = 0; s < seqs.size(); ++s) vad_segments_of(pr[s], seqs[s].x, seqs[s].n, &seqs[s].mask, &seqs[s].segs);
+    } else {
+      for (Seq& s : seqs) s.segs.push_back({0.0, (double)s.n / 16000.0, s.x, s.n});
+    }
+    // groups: every sequence but, under channel split, a channel without speech (it contributes
+    // nothing and does not take part in the file's detected language)
+    std::vector<wdr_speech_segment> segs;
+    std::vector<size_t> gs{0};
+    std::vector<const char*> spk;
+    std::vector<size_t> group_file;
+    for (Seq& s : seqs) {
+      if (e->channel_split && s.segs.empty()) continue;
+      s.group = (long long)group_file.size();
+      segs.insert(segs.end(), s.segs.begin(), s.segs.end());
+      gs.push_back(segs.size());
+      spk.push_back(e->channel_split ? s.label.c_str() : nullptr);
+      group_file.push_back(s.file);
+    }
+    std::vector<std::vector<Seg>> res;
+    std::vector<GroupLang> langs;
+    if (!group_file.empty()) {
+      if (it == e->contexts.end())
+        it = e->contexts.emplace(model, make_context(model, e->cfg.has_gpu_device, e->cfg.gpu_device, e->cfg.use_gpu,
+                                                     e->cfg.enable_dtw, e->syn, model_path))
+                 .first;
+      wdr_context* c = it->second.get();
+      struct Adapt {   // the pipeline's callbacks -> the batch's, with the file of the current group
+        const wdr_batch_callbacks* cb;
+        const std::vector<size_t>* group_file;
+        size_t group = 0;
+        static void progress(void* u, int32_t pct, int32_t type, const char* label) {
+          const Adapt* a = (const Adapt*)u;
+          a->cb->progress(a->cb->user, pct, type, label);
+        }
+        static void new_segment(void* u, const wdr_segment* seg) {
+          const Adapt* a = (const Adapt*)u;
+          a->cb->new_segment(a->cb->user, (*a->group_file)[a->group], seg);
+        }
+        static int is_cancelled(void* u) {
+          const Adapt* a = (const Adapt*)u;
+          return a->cb->is_cancelled(a->cb->user);
+        }
+      } ad{cb, &group_file};
+      wdr_callbacks wcb{};
+      if (cb) {
+        wcb.user = &ad;
+        wcb.progress = cb->progress ? &Adapt::progress : nullptr;
+        wcb.new_segment = cb->new_segment ? &Adapt::new_segment : nullptr;
+        wcb.is_cancelled = cb->is_cancelled ? &Adapt::is_cancelled : nullptr;
+      }
+      const double t = now_s();
+      c->st->times = StageTimes{};
+      c->cs = wdr_context::ChainStats{};
+      res = run_pipeline_groups(c, segs, gs, o, nullptr, e->syn, cb ? &wcb : nullptr, &langs, false, nullptr, &spk,
+                                &ad.group);
+      c->st->times.glue = now_s() - t;
+    }
+    // per file: the preset of the detected (else requested) language + overrides, process_segments
+    // with the sequence's own VAD mask; channel split labels and merges the channels' lists
+    const std::string req = (o && o->lang) ? std::string(o->lang) : std::string("auto");
+    auto finish = [&](Seq& s) {
+      const GroupLang& gl = langs[(size_t)s.group];
+      PostProcessConfig pcfg = config_for_language(gl.has ? gl.lang : req);
+      apply_overrides(pcfg, fmt);
+      return from_fmt(process_segments(to_fmt(res[(size_t)s.group]), pcfg, vad ? &s.mask : nullptr));
+    };
+    std::vector<std::vector<Seg>> fin(n_files);
+    std::vector<GroupLang> fin_lang(n_files);
+    for (size_t i = 0; i < n_files; ++i) {
+      File& f = files[i];
+      if (!f.ok) continue;
+      if (!e->channel_split) {
+        Seq& s = seqs[f.seq0];
+        fin[i] = finish(s);
+        fin_lang[i] = langs[(size_t)s.group];
+        continue;
+      }
+      std::vector<Seg>& all = fin[i];
+      std::string& lang = fin_lang[i].lang;
+      bool& has_lang = fin_lang[i].has;
+      for (int c = 0; c < f.n_ch; ++c) {
+        Seq& s = seqs[f.seq0 + (size_t)c];
+        if (s.group < 0) continue;
+        for (Seg& x : finish(s)) {
+          x.has_speaker = true;
+          x.speaker = s.label;
+          all.push_back(std::move(x));
+        }
+        const GroupLang& gl = langs[(size_t)s.group];
+        if (gl.has && !has_lang) {
+          lang = gl.lang;
+          has_lang = true;
+        }
+      }
+      std::stable_sort(all.begin(), all.end(), [](const Seg& a, const Seg& b) { return a.start < b.start; });
+    }
+    // nothing below throws: the lists are handed over whole or not at all
+    *out = (wdr_batch_item*)calloc(n_files, sizeof(wdr_batch_item));
+    for (size_t i = 0; i < n_files; ++i) {
+      if (files[i].ok) (*out)[i].list = to_list(fin[i], fin_lang[i].has ? &fin_lang[i].lang : nullptr);
+      else (*out)[i].error = strdup(files[i].err.c_str());
+    }
+    return 0;
+  })
+}
+
+void wdr_batch_free(wdr_batch_item* items, size_t n_files) {
+  if (!items) return;
+  for (size_t i = 0; i < n_files; ++i) {
+    wdr_segment_list_free(items[i].list);
+    free((void*)items[i].error);
+  }
+  free(items);
+}
+
+static void fill_stage_times(const wdr_context* c, wdr_stage_times* o);
+int wdr_engine_stage_times(wdr_engine* e, const char* model, wdr_stage_times* out) {
+  WDR_GUARD({
+    WDR_USE(eng, e);
+    auto it = e->contexts.find(model ? model : "base");
+    if (it == e->contexts.end()) return fail("engine: no context of that model yet");
+    fill_stage_times(it->second.get(), out);
+    return 0;
+  })
+}
+
 int wdr_vad_create(const char* model_path, int8_t has_gpu_device, int32_t gpu_device, wdr_vad** out) {
   WDR_GUARD({
     if (model_path && !file_exists(model_path)) return fail(std::string("VAD model file doesn't exist: ") + model_path);
@@ -1726,6 +2024,24 @@ int wdr_vad_probs(wdr_vad* v, const int16_t* samples, size_t n, float* probs_out
     WDR_USE(vad, v);
     const std::vector<float> p = v->m->probs(samples, n);
     if (!p.empty()) memcpy(probs_out, p.data(), p.size() * 4);
+    if (us_per_step) *us_per_step = v->m->last_scan_us_per_step;
+    return 0;
+  })
+}
+
+int wdr_vad_probs_batch(wdr_vad* v, const int16_t* const* samples, const size_t* n, int32_t B, float* probs_out,
+                        double* us_per_step) {
+  WDR_GUARD({
+    WDR_USE(vad, v);
+    if (B < 0 || (B > 0 && (!samples || !n))) return fail("VAD batch: NULL arrays or a negative count");
+    for (int32_t b = 0; b < B; ++b)
+      if (n[b] && !samples[b]) return fail("VAD batch: a sequence with samples is NULL");
+    const std::vector<std::vector<float>> p = v->m->probs_batch(samples, n, B);
+    size_t o = 0;
+    for (const std::vector<float>& q : p) {
+      if (!q.empty()) memcpy(probs_out + o, q.data(), q.size() * 4);
+      o += q.size();
+    }
     if (us_per_step) *us_per_step = v->m->last_scan_us_per_step;
     return 0;
   })
@@ -2204,6 +2520,31 @@ int wdr_run_pipeline(wdr_context* c, const wdr_speech_segment* segs, size_t n_se
   })
 }
 
+int wdr_run_pipeline_groups(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs, const size_t* group_start,
+                            size_t n_groups, const char* const* group_speaker, const wdr_transcribe_options* o,
+                            const wdr_synthetic* syn, const wdr_callbacks* cb, wdr_segment_list** out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    const std::vector<size_t> gs = group_bounds(group_start, n_groups, n_segs);   // before any GPU work
+    if (n_groups > 1 && o && o->enable_diarize == 1)
+      return fail("segment groups do not diarize: more than one group with diarization on");
+    if (n_groups == 0) return 0;
+    if (n_segs && !segs) return fail("segment groups: segs is NULL");
+    std::vector<wdr_speech_segment> v(segs, segs + n_segs);
+    std::vector<const char*> spk(n_groups, nullptr);
+    if (group_speaker) spk.assign(group_speaker, group_speaker + n_groups);
+    std::vector<GroupLang> langs;
+    const double t = now_s();
+    c->st->times = StageTimes{};
+    c->cs = wdr_context::ChainStats{};
+    std::vector<std::vector<Seg>> res =
+        run_pipeline_groups(c, v, gs, o, nullptr, syn_of(syn), cb, &langs, false, nullptr, &spk);
+    c->st->times.glue = now_s() - t;
+    for (size_t g = 0; g < n_groups; ++g) out[g] = to_list(res[g], langs[g].has ? &langs[g].lang : nullptr);
+    return 0;
+  })
+}
+
 int wdr_run_pipeline_raw(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
                          const wdr_transcribe_options* o, const wdr_synthetic* syn, wdr_segment_list** out) {
   WDR_GUARD({
@@ -2354,9 +2695,8 @@ int wdr_context_set_chains(wdr_context* c, int32_t n) {
   })
 }
 
-int wdr_context_stage_times(wdr_context* c, wdr_stage_times* o) {
-  WDR_GUARD({
-    WDR_USE(ctx, c);
+static void fill_stage_times(const wdr_context* c, wdr_stage_times* o) {
+  {
     const StageTimes& t = c->st->times;
     *o = wdr_stage_times{t.mel,          t.encode,   t.decode,  t.dtw,        0.0,  t.glue, t.windows,
                          t.decode_steps, t.prefills, t.lang,    t.prompt_gpu, c->embed_s};
@@ -2381,6 +2721,13 @@ int wdr_context_stage_times(wdr_context* c, wdr_stage_times* o) {
     o->dtwq_jobs = c->cs.dq_jobs;
     o->lang_passes = t.lang_passes;
     o->lang_rows = t.lang_rows;
+  }
+}
+
+int wdr_context_stage_times(wdr_context* c, wdr_stage_times* o) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    fill_stage_times(c, o);
     return 0;
   })
 }

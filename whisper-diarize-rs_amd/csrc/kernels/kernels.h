@@ -191,6 +191,10 @@ struct VadWeights {
 };
 void launch_vad(const float* x, long long n, const VadWeights& w, float* xg, float* hout, float* probs,
                 hipStream_t s);
+// B sequences in one pass: x holds them back to back, each zero-padded to whole chunks (n = nc * 512);
+// off[0 .. B] (device) are the sequences' chunk offsets into xg / hout / probs
+void launch_vad_batch(const float* x, long long n, const long long* off, int B, long long nc, const VadWeights& w,
+                      float* xg, float* hout, float* probs, hipStream_t s);
 
 // Diarization (kernels/diar.hip), all f32
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2, ACT_SIGMOID = 3, ACT_ABS = 4 };

@@ -12,6 +12,8 @@
 //                f16 hidden state in LDS (double-buffered, one barrier per step); the pair
 //                combines with one shuffle and both update (c, h) redundantly.  xg is
 //                prefetched kPF steps ahead.  Latency-bound chain: reported in us/step.
+//  k_vad_lstm_batch  B recordings in one launch: one workgroup per recurrence over a concatenated
+//                xg, the same scan body.
 //  k_vad_head    p = sigmoid(w_o . f16(relu(h)) + b_o), one wave per chunk.
 #include "../common.h"
 #include "kernels.h"
@@ -134,8 +136,10 @@ __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v))
 
 constexpr int kPF = 8;   // xg prefetch depth (steps)
 
-__global__ __launch_bounds__(256) void k_vad_lstm(const float* __restrict__ xg, long long n_steps, VadWeights w,
-                                                  float* __restrict__ hout) {
+// One sequence's scan by one workgroup: n_steps chunks of xg -> hout.  Shared by the single and
+// the batched kernel so that a sequence's hout is the same bits from either.
+__device__ __forceinline__ void vad_lstm_scan(const float* __restrict__ xg, long long n_steps, VadWeights w,
+                                              float* __restrict__ hout) {
   __shared__ f16 hs[2][128];
   const int tid = threadIdx.x;
   const int u = tid >> 1, part = tid & 1;
@@ -196,6 +200,22 @@ __global__ __launch_bounds__(256) void k_vad_lstm(const float* __restrict__ xg, 
   }
 }
 
+__global__ __launch_bounds__(256) void k_vad_lstm(const float* __restrict__ xg, long long n_steps, VadWeights w,
+                                                  float* __restrict__ hout) {
+  vad_lstm_scan(xg, n_steps, w, hout);
+}
+
+// B independent recurrences, one workgroup each: sequence b owns chunks [off[b], off[b+1]) of the
+// concatenated xg / hout.  The scan is told its own length, so the xg prefetch stops at off[b+1]
+// (never past the last sequence's end), and a sequence without chunks leaves before the first
+// barrier -- the whole workgroup does, blockIdx decides -- without touching memory.
+__global__ __launch_bounds__(256) void k_vad_lstm_batch(const float* __restrict__ xg, const long long* __restrict__ off,
+                                                        VadWeights w, float* __restrict__ hout) {
+  const long long a = off[blockIdx.x], n_steps = off[blockIdx.x + 1] - a;
+  if (n_steps <= 0) return;
+  vad_lstm_scan(xg + a * 512, n_steps, w, hout + a * 128);
+}
+
 __global__ __launch_bounds__(256) void k_vad_head(const float* __restrict__ hout, long long n_steps, VadWeights w,
                                                   float* __restrict__ probs) {
   const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -215,6 +235,20 @@ void launch_vad(const float* x, long long n, const VadWeights& w, float* xg, flo
   WDR_KLAUNCH(k_vad_front, dim3((unsigned)nc), dim3(256), 0, s, x, n, w, xg);
   WDR_HIP(hipGetLastError());
   WDR_KLAUNCH(k_vad_lstm, dim3(1), dim3(256), 0, s, xg, nc, w, hout);
+  WDR_HIP(hipGetLastError());
+  WDR_KLAUNCH(k_vad_head, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, hout, nc, w, probs);
+  WDR_HIP(hipGetLastError());
+}
+
+// x: the sequences' samples back to back, each zero-padded to a multiple of 512 (n = the padded
+// total, so the front end's `s < n ? x[s] : 0` never cuts in); off[0 .. B]: chunk offsets
+void launch_vad_batch(const float* x, long long n, const long long* off, int B, long long nc, const VadWeights& w,
+                      float* xg, float* hout, float* probs, hipStream_t s) {
+  if (nc <= 0 || B <= 0) return;
+  WDR_CHECK(nc < (1ll << 31) && n == nc * 512, "VAD: bad batch size");
+  WDR_KLAUNCH(k_vad_front, dim3((unsigned)nc), dim3(256), 0, s, x, n, w, xg);
+  WDR_HIP(hipGetLastError());
+  WDR_KLAUNCH(k_vad_lstm_batch, dim3((unsigned)B), dim3(256), 0, s, xg, off, w, hout);
   WDR_HIP(hipGetLastError());
   WDR_KLAUNCH(k_vad_head, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, hout, nc, w, probs);
   WDR_HIP(hipGetLastError());

@@ -2,8 +2,10 @@
 // probability -> segment state machine.  Mirrors oracle/vad.py (test-only restatement).
 #include "vad.h"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 
 #include "model_files.h"
 #include "prof.h"
@@ -126,6 +128,51 @@ std::vector<float> VadModel::probs(const int16_t* pcm, size_t n) {
   float ms = 0.f;
   WDR_HIP(hipEventElapsedTime(&ms, e0_, e1_));
   last_scan_us_per_step = ms * 1e3 / (double)nc;
+  return out;
+}
+
+std::vector<std::vector<float>> VadModel::probs_batch(const int16_t* const* pcm, const size_t* n, int B) {
+  WDR_HIP(hipSetDevice(device));
+  std::vector<std::vector<float>> out(std::max(B, 0));
+  std::vector<long long> off(std::max(B, 0) + 1, 0);
+  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (long long)((n[b] + 511) / 512);
+  const size_t nc = (size_t)off.back();
+  last_scan_us_per_step = 0.0;
+  if (nc == 0) return out;
+  WDR_CHECK(nc * 512 < (size_t)INT_MAX, "VAD: batch too long");
+  // one staging image, one upload: the chunk offsets, then every sequence's samples padded with
+  // zeros to whole chunks (what the front end's `s < n ? x[s] : 0` gives a sequence on its own)
+  const size_t off_bytes = off.size() * sizeof(long long);
+  std::vector<char> img(off_bytes + nc * 512 * 2, 0);
+  memcpy(img.data(), off.data(), off_bytes);
+  int16_t* dst = reinterpret_cast<int16_t*>(img.data() + off_bytes);
+  for (int b = 0; b < B; ++b)
+    if (n[b]) memcpy(dst + (size_t)off[b] * 512, pcm[b], n[b] * 2);
+  if (img.size() > bimg_cap_) {
+    bimg_ = DevMem(img.size());
+    bimg_cap_ = img.size();
+  }
+  if (nc > bcap_) {
+    bx_ = DevMem(nc * 512 * 4);
+    bxg_ = DevMem(nc * 512 * 4);
+    bhout_ = DevMem(nc * 128 * 4);
+    bprobs_ = DevMem(nc * 4);
+    bcap_ = nc;
+  }
+  WDR_HIP(wdr_memcpy_async(bimg_.p, img.data(), img.size(), hipMemcpyHostToDevice, s_));
+  const int16_t* dpcm = reinterpret_cast<const int16_t*>(bimg_.as<char>() + off_bytes);
+  launch_i16_to_f32(dpcm, (int)(nc * 512), bx_.as<float>(), s_);
+  WDR_HIP(hipEventRecord(e0_, s_));
+  launch_vad_batch(bx_.as<float>(), (long long)(nc * 512), bimg_.as<long long>(), B, (long long)nc, vw_,
+                   bxg_.as<float>(), bhout_.as<float>(), bprobs_.as<float>(), s_);
+  WDR_HIP(hipEventRecord(e1_, s_));
+  std::vector<float> all(nc);
+  WDR_HIP(wdr_memcpy_async(all.data(), bprobs_.p, nc * 4, hipMemcpyDeviceToHost, s_));
+  WDR_HIP(hipStreamSynchronize(s_));
+  float ms = 0.f;
+  WDR_HIP(hipEventElapsedTime(&ms, e0_, e1_));
+  last_scan_us_per_step = ms * 1e3 / (double)nc;
+  for (int b = 0; b < B; ++b) out[b].assign(all.begin() + off[b], all.begin() + off[b + 1]);
   return out;
 }
 

@@ -24,6 +24,9 @@ class VadModel {
   ~VadModel();
   // speech probability per 512-sample chunk of int16 PCM (x / 32768 as src/vad.rs:11-12)
   std::vector<float> probs(const int16_t* pcm, size_t n);
+  // the same for B independent sequences in one pass (one upload, three launches, one sync): the
+  // recurrences run one workgroup each; result b is bit-identical to probs(pcm[b], n[b])
+  std::vector<std::vector<float>> probs_batch(const int16_t* const* pcm, const size_t* n, int B);
   double last_scan_us_per_step = 0.0;   // LSTM chain latency of the last call
   int device;
 
@@ -33,6 +36,8 @@ class VadModel {
   VadWeights vw_{};
   DevMem pcm_, x_, xg_, hout_, probs_;
   size_t cap_ = 0;
+  DevMem bimg_, bx_, bxg_, bhout_, bprobs_;   // probs_batch: staging image (offsets + int16), then as above
+  size_t bimg_cap_ = 0, bcap_ = 0;            // bytes, chunks
   hipEvent_t e0_ = nullptr, e1_ = nullptr;
 };
 

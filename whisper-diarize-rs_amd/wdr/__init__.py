@@ -19,7 +19,7 @@ from . import _lib as L
 __all__ = ["Engine", "EngineConfig", "TranscribeOptions", "AdvancedTranscribe", "DiarizeOptions", "Segment",
            "WordTimestamp",
            "ProgressType", "Callbacks", "Synthetic", "WhisperContext", "SpeechSegment", "read_wav", "vad_merge",
-           "WdrError"]
+           "WdrError", "BatchResult", "BatchCallbacks"]
 
 WdrError = L.WdrError
 
@@ -95,6 +95,23 @@ class Callbacks:                           # src/engine.rs:35-40
     progress: Optional[Callable[[int, ProgressType, str], None]] = None
     new_segment_callback: Optional[Callable[[Segment], None]] = None
     is_cancelled: Optional[Callable[[], bool]] = None
+
+
+@dataclasses.dataclass
+class BatchCallbacks:
+    """Callbacks of Engine.transcribe_batch: new_segment_callback also gets the file's index."""
+    progress: Optional[Callable[[int, ProgressType, str], None]] = None
+    new_segment_callback: Optional[Callable[[int, Segment], None]] = None
+    is_cancelled: Optional[Callable[[], bool]] = None
+
+
+@dataclasses.dataclass
+class BatchResult:
+    """One file of Engine.transcribe_batch: its segments and detected language, or the error the
+    single call would have raised for it (then segments is None)."""
+    segments: Optional[List[Segment]] = None
+    detected_lang: Optional[str] = None
+    error: Optional[str] = None
 
 
 @dataclasses.dataclass
@@ -250,7 +267,7 @@ def process_segments(segments: List[Segment], lang: str = "auto", overrides: Opt
     return _segments(out)[0]
 
 
-def _segments(lst_ptr, with_index: bool = False) -> tuple:
+def _segments(lst_ptr, with_index: bool = False, free: bool = True) -> tuple:
     lst = lst_ptr.contents
     index = [int(lst.speech_index[i]) for i in range(lst.n_segments)] if lst.speech_index else None
     out = []
@@ -264,7 +281,8 @@ def _segments(lst_ptr, with_index: bool = False) -> tuple:
         out.append(Segment(s.start, s.end, s.text.decode("utf-8", "replace"), words,
                            s.speaker_id.decode() if s.speaker_id else None))
     lang = lst.detected_lang.decode() if lst.detected_lang else None
-    L.load().wdr_segment_list_free(lst_ptr)
+    if free:
+        L.load().wdr_segment_list_free(lst_ptr)
     return (out, lang, index) if with_index else (out, lang)
 
 
@@ -469,6 +487,23 @@ class Vad:
                                         out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(us)))
         self.last_us_per_step = us.value
         return out
+
+    def probs_batch(self, sequences) -> list:
+        """probs() of several independent recordings in one pass (wdr_vad_probs_batch: one upload,
+        three launches, one sync; the LSTM scans run side by side, one workgroup each).  Returns one
+        array per sequence, bit-identical to probs() of it; empty sequences are legal."""
+        smp = [np.ascontiguousarray(x, np.int16).reshape(-1) for x in sequences]
+        B = len(smp)
+        ptrs = (C.POINTER(C.c_int16) * max(B, 1))(*[x.ctypes.data_as(C.POINTER(C.c_int16)) for x in smp])
+        ns = (C.c_size_t * max(B, 1))(*[x.size for x in smp])
+        cnt = [(x.size + 511) // 512 for x in smp]
+        out = np.zeros(max(1, sum(cnt)), np.float32)
+        us = C.c_double()
+        L.check(self._lib.wdr_vad_probs_batch(self.h, ptrs, ns, B, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                              C.byref(us)))
+        self.last_us_per_step = us.value
+        ends = np.cumsum([0] + cnt)
+        return [out[ends[b]:ends[b + 1]].copy() for b in range(B)]
 
     def get_segments(self, samples: np.ndarray, materialize: bool = True):
         """-> (mask [(start_s, end_s)], [SpeechSegment]) exactly as vad::get_segments.
@@ -807,6 +842,38 @@ class WhisperContext:
                                            C.byref(out)))
         return _segments(out, with_index)
 
+    def run_pipeline_groups(self, groups, options: TranscribeOptions, speakers=None,
+                            callbacks: Optional[Callbacks] = None, synthetic: Optional[Synthetic] = None,
+                            with_index: bool = False, group_start=None):
+        """Several independent recordings' speech segments in one pipeline run
+        (wdr_run_pipeline_groups): groups is a list of lists of SpeechSegment; the result is one
+        (segments, detected_lang) [+ speech index] per group, each equal to run_pipeline(group, ...)
+        without diarization, while the decode chains are shared by all groups.  speakers: an
+        optional fixed speaker_id per group (entries may be None).  group_start (test seam): pass
+        the raw group_start array with groups as one flat list of segments."""
+        keep = _Keep()
+        if group_start is None:
+            flat = [s for g in groups for s in g]
+            starts = list(np.cumsum([0] + [len(g) for g in groups])[:-1])
+        else:
+            flat, starts = list(groups), [int(x) for x in group_start]
+        G = len(starts)
+        arr = (L.SpeechSegment * max(1, len(flat)))()
+        for i, s in enumerate(flat):
+            smp = keep(np.ascontiguousarray(s.samples, np.int16))
+            arr[i] = L.SpeechSegment(s.start, s.end, smp.ctypes.data_as(C.POINTER(C.c_int16)), smp.size)
+        gs = (C.c_size_t * max(1, G))(*[int(x) for x in starts])
+        spk = None
+        if speakers is not None:
+            if len(speakers) != G:
+                raise ValueError("one speaker entry per group")
+            spk = (C.c_char_p * max(1, G))(*[_s(x) for x in speakers])
+        out = (C.POINTER(L.SegmentList) * max(1, G))()
+        syn = _syn(synthetic or self.synthetic)
+        L.check(self._lib.wdr_run_pipeline_groups(self.h, arr, len(flat), gs, G, spk, _opts(options, keep),
+                                                  C.byref(syn) if syn else None, _callbacks(callbacks, keep), out))
+        return [_segments(out[g], with_index) for g in range(G)]
+
     def run_pipeline_raw(self, speech_segments, options: TranscribeOptions, synthetic: Optional[Synthetic] = None):
         """run_pipeline without the cross-segment overlap clip and speaker assignment
         (wdr_run_pipeline_raw): (segments, detected_lang, speech index per segment)."""
@@ -1073,6 +1140,59 @@ class Engine:
                                                _callbacks(cb, keep), C.byref(out)))
         segs, _ = _segments(out)
         return segs
+
+    def transcribe_batch(self, paths, options: TranscribeOptions, overrides=None,
+                         callbacks: Optional[BatchCallbacks] = None) -> List[BatchResult]:
+        """Many recordings in one call (wdr_transcribe_batch): result i holds what
+        transcribe_audio(paths[i], options, overrides) returns on this engine (and the detected
+        language), the decode chains and the VAD pass shared by all files.  A file that cannot be
+        read gets its error instead; the others are unaffected.  enable_diarize is refused."""
+        keep = _Keep()
+        n = len(paths)
+        arr = (C.c_char_p * max(1, n))(*[_s(p) for p in paths])
+        ov = _fmt(overrides)
+        cbs = None
+        if callbacks is not None:
+            cbs = L.BatchCallbacks()
+            if callbacks.progress:
+                cbs.progress = keep(L.PROGRESS_FN(
+                    lambda u, p, t, lbl: callbacks.progress(int(p), ProgressType(t), lbl.decode())))
+            if callbacks.new_segment_callback:
+                def seg_cb(u, idx, sp):
+                    s = sp.contents
+                    words = None
+                    if s.words:
+                        words = [WordTimestamp(s.words[k].text.decode(), s.words[k].start, s.words[k].end,
+                                               s.words[k].probability if s.words[k].has_probability else None)
+                                 for k in range(s.n_words)]
+                    callbacks.new_segment_callback(int(idx), Segment(s.start, s.end, s.text.decode(), words,
+                                                                     s.speaker_id.decode() if s.speaker_id else None))
+                cbs.new_segment = keep(L.BATCH_SEGMENT_FN(seg_cb))
+            if callbacks.is_cancelled:
+                cbs.is_cancelled = keep(L.CANCEL_FN(lambda u: 1 if callbacks.is_cancelled() else 0))
+        items = C.POINTER(L.BatchItem)()
+        L.check(self._lib.wdr_transcribe_batch(self.h, arr if paths is not None else None, n, _opts(options, keep),
+                                               C.byref(ov) if ov is not None else None,
+                                               C.byref(cbs) if cbs is not None else None, C.byref(items)))
+        out = []
+        try:
+            for i in range(n):
+                it = items[i]
+                if it.error:
+                    out.append(BatchResult(None, None, C.cast(it.error, C.c_char_p).value.decode("utf-8", "replace")))
+                else:
+                    segs, lang = _segments(it.list, free=False)
+                    out.append(BatchResult(segs, lang, None))
+        finally:
+            self._lib.wdr_batch_free(items, n)
+        return out
+
+    def stage_times(self, model: str = "base") -> dict:
+        """Stage accounting of the engine's context of `model` after its last call
+        (wdr_engine_stage_times; WhisperContext.stage_times' fields)."""
+        t = L.StageTimes()
+        L.check(self._lib.wdr_engine_stage_times(self.h, model.encode(), C.byref(t)))
+        return {f: getattr(t, f) for f, _ in L.StageTimes._fields_}
 
     def close(self):
         if self.h:

@@ -83,6 +83,18 @@ class Callbacks(C.Structure):
     _fields_ = [("user", vp), ("progress", PROGRESS_FN), ("new_segment", SEGMENT_FN), ("is_cancelled", CANCEL_FN)]
 
 
+BATCH_SEGMENT_FN = C.CFUNCTYPE(None, vp, sz, C.POINTER(Segment))
+
+
+class BatchCallbacks(C.Structure):
+    _fields_ = [("user", vp), ("progress", PROGRESS_FN), ("new_segment", BATCH_SEGMENT_FN),
+                ("is_cancelled", CANCEL_FN)]
+
+
+class BatchItem(C.Structure):
+    _fields_ = [("list", C.POINTER(SegmentList)), ("error", vp)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("mel", f64), ("encode", f64), ("decode", f64), ("dtw", f64), ("vad", f64), ("total", f64),
                 ("windows", i64), ("decode_steps", i64), ("prefills", i64), ("lang", f64), ("prompt_gpu", f64),
@@ -121,6 +133,10 @@ _SIGS = {
     "wdr_engine_set_synthetic": (C.c_int, [vp, P(Synthetic)]),
     "wdr_transcribe_audio": (C.c_int, [vp, cstr, P(TranscribeOptions), P(FormattingOverrides), P(Callbacks),
                                        P(P(SegmentList))]),
+    "wdr_transcribe_batch": (C.c_int, [vp, P(cstr), sz, P(TranscribeOptions), P(FormattingOverrides),
+                                       P(BatchCallbacks), P(P(BatchItem))]),
+    "wdr_batch_free": (None, [P(BatchItem), sz]),
+    "wdr_engine_stage_times": (C.c_int, [vp, cstr, P(StageTimes)]),
     "wdr_read_wav": (C.c_int, [cstr, P(P(C.c_int16)), P(sz)]),
     "wdr_audio_info": (C.c_int, [cstr, P(i32), P(u64)]),
     "wdr_read_audio": (C.c_int, [cstr, i8, i32, P(P(C.c_int16)), P(sz)]),
@@ -138,6 +154,7 @@ _SIGS = {
     "wdr_vad_create": (C.c_int, [cstr, i8, i32, P(vp)]),
     "wdr_vad_free": (None, [vp]),
     "wdr_vad_probs": (C.c_int, [vp, P(C.c_int16), sz, P(f32), P(f64)]),
+    "wdr_vad_probs_batch": (C.c_int, [vp, P(P(C.c_int16)), P(sz), i32, P(f32), P(f64)]),
     "wdr_vad_stats": (C.c_int, [vp, P(f64)]),
     "wdr_vad_segments_from_probs": (C.c_int, [P(f32), sz, P(f32), P(sz)]),
     "wdr_vad_get_segments": (C.c_int, [vp, P(C.c_int16), sz, P(P(f64)), P(sz), P(P(SpeechSegment)), P(sz)]),
@@ -159,6 +176,8 @@ _SIGS = {
                                        P(P(SegmentList))]),
     "wdr_run_pipeline": (C.c_int, [vp, P(SpeechSegment), sz, P(TranscribeOptions), P(DiarizeOptions), P(Synthetic),
                                    P(Callbacks), P(P(SegmentList))]),
+    "wdr_run_pipeline_groups": (C.c_int, [vp, P(SpeechSegment), sz, P(sz), sz, P(cstr), P(TranscribeOptions),
+                                          P(Synthetic), P(Callbacks), P(P(SegmentList))]),
     "wdr_run_pipeline_block": (C.c_int, [vp, P(SpeechSegment), sz, P(TranscribeOptions), P(Synthetic), cstr, P(i8),
                                          P(C.c_void_p), P(P(SegmentList))]),
     "wdr_segment_list_free": (None, [P(SegmentList)]),
