@@ -496,6 +496,9 @@ int wdr_state_full(wdr_context* c, const float* samples, size_t n, const wdr_tra
 void wdr_result_free(wdr_result_seg* segs, size_t n);
 
 /* ---- kernel-level test seams (host buffers in / out) ---- */
+/* the normalised log-mel window at frame `seek`, f32: the double normalisation rounded to odd (within
+ * one f32 ulp of the nearest f32), so that rounding it to f16 gives exactly the conv1 operand every
+ * production encode stores (one double -> f16 rounding; wdr_dbg_im2col_mel) */
 int wdr_dbg_log_mel(wdr_context* c, const float* x, size_t n, int32_t seek, float* window_out /* [n_mels][3000] */);
 int wdr_dbg_energy(const float* x, size_t n, float* out);
 /* the load-time dequantization kernel: n_blocks raw blocks of ggml type 2 / 3 / 6 / 7 / 8 ->
@@ -619,6 +622,47 @@ int wdr_dbg_kv_rows(wdr_context* c, int32_t seq, int32_t n_rows, int32_t write, 
  * n_rows cached rows that sequence src[i] held before the call, i < n <= 8; a destination named twice
  * is an error */
 int wdr_dbg_kv_reorder(wdr_context* c, const int32_t* src, const int32_t* dst, int32_t n, int32_t n_rows);
+
+/* ---- encoder seams.  Every one checks its arguments on the host and returns an error instead of
+ * launching on a bad shape ---- */
+/* the bit patterns an encoder seam's device output holds before the launch (NaNs no finite result
+ * rounds to): an element the kernel never wrote comes back as one of them */
+#define WDR_DBG_SENTINEL_F16 0x7e57
+#define WDR_DBG_SENTINEL_F32 0x7fc07e57u
+/* conv1's operand as every production encode builds it: the log-mel of x[0 .. n) (as wdr_dbg_log_mel),
+ * then k_im2col_mel at frame `seek` exactly as an on-demand window encode launches it.  out_f16
+ * [3000][kp] raw f16 bits, row t column 3 ci + k = the normalised log-mel of channel ci at window
+ * frame t + k - 1 (0 outside 0 .. 2999), columns [3 n_mels, kp) +0.  kp_out = kp (the model's
+ * 3 n_mels rounded up to 32); out_f16 null: only kp_out is set */
+int wdr_dbg_im2col_mel(wdr_context* c, const float* x, size_t n, int32_t seek, uint16_t* out_f16, int32_t* kp_out);
+/* the encoder-only epilogues of the tiled GEMMs (M > 64, N % 128, K % 32; a [M][K], w [N][K] f16 bits,
+ * bias [N] nullable) launched as the encoder launches them; gemm_ref != 0: on the reference tile
+ * k_gemm (as WDR_DBG_PROJ_GEMM1), bit-identical to what the dispatch rule picks.
+ * epi 4: out f32 [M][N] = gelu(a w^T + bias) + pos[row % pos_rows] (pos [pos_rows][N]; slot_elems unused).
+ * epi 6: out f16 bits [M / 1500][slot_elems], the raw cross-K/V slot image of every 1500-row window:
+ * column c of row 1500 w + t at slot w, element (c / 64) * 96000 + 64 t + c % 64; needs M % 1500 == 0
+ * and slot_elems >= 1500 N (a multiple of 4); pos / pos_rows unused.
+ * The device buffer holds the sentinel before the launch and comes back whole */
+int wdr_dbg_proj_enc(const uint16_t* a_f16, const uint16_t* w_f16, const float* bias, const float* pos,
+                     int32_t pos_rows, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gemm_ref,
+                     int64_t slot_elems, void* out);
+/* the encoder's self-attention over nb stacked windows in one launch, with the encoder's own launch
+ * arguments: qkv [nb][T][3 * 64 H] f16 bits (Q, K, V of a row side by side, as the qkv projection
+ * writes them), non-causal, scale 1/8; out [nb][T][64 H] (f16 -> f32).  nb <= 16, T <= 4096 */
+int wdr_dbg_attn_batch(const uint16_t* qkv_f16, int32_t nb, int32_t T, int32_t H, float* out);
+/* k_layernorm alone (eps 1e-5, biased variance): x [rows][ldx] f32, g / b [d]; out [rows][d] (f16 ->
+ * f32), row r from x row r (row_map null: launch_layernorm) or x row row_map[r] (in [0, rows):
+ * launch_layernorm_rows).  d % 4 == 0, d <= 1280, ldx % 4 == 0, ldx >= d */
+int wdr_dbg_layernorm(const float* x, int32_t ldx, const float* g, const float* b, int32_t rows, int32_t d,
+                      const int32_t* row_map, float* out);
+/* one encode-ahead batch without a plan: clip k (int16 PCM, n[k] >= 1 samples) goes through the
+ * front half of the encode-ahead loop on ring slot k (samples, log-mel, conv1 operand rows k of the
+ * batch buffers, window 0), then the batched encoder runs once over the nb stacked windows (nb = 1
+ * .. 4, the encode-ahead batch) into ring slots 0 .. nb - 1 -- no graph, language detection or
+ * events.  enc_out [nb][1500][d] (f16 -> f32), xkv_out [nb][1500][n_text_layer][2][d] as
+ * wdr_dbg_cross_kv.  The state must be idle (no pipeline running on the context) */
+int wdr_dbg_encode_batch(wdr_context* c, const int16_t* const* pcm, const int32_t* n, int32_t nb, float* enc_out,
+                         float* xkv_out);
 
 #ifdef __cplusplus
 }

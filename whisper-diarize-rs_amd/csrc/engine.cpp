@@ -2834,6 +2834,32 @@ int wdr_dbg_cross_kv(wdr_context* c, float* out) {
   })
 }
 
+int wdr_dbg_im2col_mel(wdr_context* c, const float* x, size_t n, int32_t seek, uint16_t* out_f16, int32_t* kp_out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(kp_out, "dbg_im2col_mel: null argument");
+    *kp_out = c->ctx->model.kp1;
+    if (!out_f16) return 0;   // the row width only
+    WDR_CHECK(x && n >= 1 && n <= (size_t)16000 * 3600, "dbg_im2col_mel: 1 sample .. 1 h of samples");
+    WDR_CHECK(seek >= 0 && seek <= 360000, "dbg_im2col_mel: seek out of range");
+    c->st->dbg_im2col_mel(x, (int)n, seek, out_f16);
+    return 0;
+  })
+}
+
+int wdr_dbg_encode_batch(wdr_context* c, const int16_t* const* pcm, const int32_t* n, int32_t nb, float* enc_out,
+                         float* xkv_out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    WDR_CHECK(pcm && n && enc_out && xkv_out, "dbg_encode_batch: null argument");
+    WDR_CHECK(nb >= 1 && nb <= 16, "dbg_encode_batch: window count out of range");
+    for (int k = 0; k < nb; ++k)
+      WDR_CHECK(pcm[k] && n[k] >= 1 && n[k] <= 16000 * 3600, "dbg_encode_batch: clips of 1 sample .. 1 h");
+    c->st->dbg_encode_batch(pcm, n, nb, enc_out, xkv_out);   // refuses nb above the encode-ahead batch
+    return 0;
+  })
+}
+
 int wdr_dbg_decode(wdr_context* c, const int32_t* tokens, size_t n, float* logits_out) {
   WDR_GUARD({
     WDR_USE(ctx, c);
@@ -3124,6 +3150,108 @@ int wdr_dbg_attn(const uint16_t* q, const uint16_t* k, const uint16_t* v, int32_
     launch_flash_attn(fa, 1, nullptr);
     std::vector<f16> h((size_t)Tq * d);
     WDR_HIP(hipMemcpy(h.data(), dout.p, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) out[i] = (float)h[i];
+    return 0;
+  })
+}
+
+// the two encoder-only epilogues of the tiled GEMM family, which wdr_dbg_proj cannot reach: conv2's
+// GELU + positional rows (EPI_F32_GELU_POS) and the cross-K/V slot scatter (EPI_XKV), launched as
+// encoder_body launches them.  The device output starts as a sentinel (f32 / f16 NaN patterns no
+// finite product rounds to) and is returned whole
+int wdr_dbg_proj_enc(const uint16_t* a16, const uint16_t* w16, const float* bias, const float* pos, int32_t pos_rows,
+                     int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gemm_ref, int64_t slot_elems, void* out) {
+  WDR_GUARD({
+    WDR_CHECK(a16 && w16 && out, "dbg_proj_enc: null argument");
+    WDR_CHECK(M > 64 && M <= (1 << 16) && N >= 128 && N <= (1 << 17) && N % 128 == 0 && K >= 32 && K <= 8192 && K % 32 == 0,
+              "dbg_proj_enc: bad shape (M > 64, N % 128, K % 32)");
+    WDR_CHECK(epi == EPI_F32_GELU_POS || epi == EPI_XKV, "dbg_proj_enc: epi 4 or 6");
+    size_t out_bytes = 0;
+    if (epi == EPI_F32_GELU_POS) {
+      WDR_CHECK(pos && pos_rows >= 1 && pos_rows <= M, "dbg_proj_enc: epi 4 needs pos [pos_rows][N], 1 <= pos_rows <= M");
+      out_bytes = (size_t)M * N * 4;
+    } else {
+      WDR_CHECK(M % XKV_T == 0, "dbg_proj_enc: epi 6 needs whole windows (M % 1500 == 0)");
+      WDR_CHECK(slot_elems >= (int64_t)N * XKV_T && slot_elems <= ((int64_t)1 << 28) && slot_elems % 4 == 0,
+                "dbg_proj_enc: epi 6 needs slot_elems >= N * 1500 (and a multiple of 4)");
+      out_bytes = (size_t)(M / XKV_T) * (size_t)slot_elems * 2;
+    }
+    DevMem da((size_t)M * K * 2), dw((size_t)N * K * 2), db(bias ? (size_t)N * 4 : 0),
+        dp(epi == EPI_F32_GELU_POS ? (size_t)pos_rows * N * 4 : 0), dout(out_bytes);
+    WDR_HIP(hipMemcpy(da.p, a16, da.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dw.p, w16, dw.bytes, hipMemcpyHostToDevice));
+    if (bias) WDR_HIP(hipMemcpy(db.p, bias, db.bytes, hipMemcpyHostToDevice));
+    if (epi == EPI_F32_GELU_POS) {
+      WDR_HIP(hipMemcpy(dp.p, pos, dp.bytes, hipMemcpyHostToDevice));
+      std::vector<uint32_t> fill((size_t)M * N, WDR_DBG_SENTINEL_F32);
+      WDR_HIP(hipMemcpy(dout.p, fill.data(), out_bytes, hipMemcpyHostToDevice));
+    } else {
+      std::vector<uint16_t> fill(out_bytes / 2, WDR_DBG_SENTINEL_F16);
+      WDR_HIP(hipMemcpy(dout.p, fill.data(), out_bytes, hipMemcpyHostToDevice));
+    }
+    ProjArgs a{da.as<f16>(), K, dw.as<f16>(), K, bias ? db.as<float>() : nullptr, dout.p, N, nullptr, 0, M, N, K, epi};
+    if (epi == EPI_F32_GELU_POS) {
+      a.pos = dp.as<float>();
+      a.pos_rows = pos_rows;
+    } else {
+      a.seq_stride = (long long)slot_elems;
+    }
+    a.gemm_ref = gemm_ref ? 1 : 0;
+    launch_proj(a, nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    WDR_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return 0;
+  })
+}
+
+// the encoder's self-attention over nb stacked windows exactly as encoder_body launches it
+// (encoder_flash_args: interleaved Q / K / V rows, per-window strides, one launch)
+int wdr_dbg_attn_batch(const uint16_t* qkv, int32_t nb, int32_t T, int32_t H, float* out) {
+  WDR_GUARD({
+    WDR_CHECK(qkv && out, "dbg_attn_batch: null argument");
+    WDR_CHECK(nb >= 1 && nb <= 16 && T >= 1 && T <= 4096 && H >= 1 && H <= 32, "dbg_attn_batch: bad shape");
+    const int d = H * 64;
+    const size_t rows = (size_t)nb * T;
+    DevMem dq(rows * 3 * d * 2), dout(rows * d * 2);
+    WDR_HIP(hipMemcpy(dq.p, qkv, dq.bytes, hipMemcpyHostToDevice));
+    std::vector<uint16_t> h(rows * d, WDR_DBG_SENTINEL_F16);
+    WDR_HIP(hipMemcpy(dout.p, h.data(), dout.bytes, hipMemcpyHostToDevice));
+    launch_flash_attn(encoder_flash_args(dq.as<f16>(), dout.as<f16>(), T, d, H), nb, nullptr);
+    WDR_HIP(hipDeviceSynchronize());
+    WDR_HIP(hipMemcpy(h.data(), dout.p, dout.bytes, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) {
+      f16 v;
+      memcpy(&v, &h[i], 2);
+      out[i] = (float)v;
+    }
+    return 0;
+  })
+}
+
+// k_layernorm through launch_layernorm (row_map null) or launch_layernorm_rows: x holds `rows` rows
+// of stride ldx, output row r = LayerNorm(x row row_map[r] or r) * g + b, f16 widened to f32
+int wdr_dbg_layernorm(const float* x, int32_t ldx, const float* g, const float* b, int32_t rows, int32_t d,
+                      const int32_t* row_map, float* out) {
+  WDR_GUARD({
+    WDR_CHECK(x && g && b && out, "dbg_layernorm: null argument");
+    WDR_CHECK(rows >= 1 && rows <= (1 << 16) && d >= 4 && d <= 1280 && d % 4 == 0 && ldx >= d && ldx <= 8192 && ldx % 4 == 0,
+              "dbg_layernorm: bad shape (d % 4, d <= 1280, ldx % 4, ldx >= d)");
+    for (int r = 0; row_map && r < rows; ++r)
+      WDR_CHECK(row_map[r] >= 0 && row_map[r] < rows, "dbg_layernorm: row_map out of range");
+    DevMem dx((size_t)rows * ldx * 4), dg((size_t)d * 4), db((size_t)d * 4), dm(row_map ? (size_t)rows * 4 : 0),
+        dy((size_t)rows * d * 2);
+    WDR_HIP(hipMemcpy(dx.p, x, dx.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(dg.p, g, dg.bytes, hipMemcpyHostToDevice));
+    WDR_HIP(hipMemcpy(db.p, b, db.bytes, hipMemcpyHostToDevice));
+    if (row_map) {
+      WDR_HIP(hipMemcpy(dm.p, row_map, dm.bytes, hipMemcpyHostToDevice));
+      launch_layernorm_rows(dx.as<float>(), ldx, dg.as<float>(), db.as<float>(), dy.as<f16>(), d, rows, d, dm.as<int>(), nullptr);
+    } else {
+      launch_layernorm(dx.as<float>(), ldx, dg.as<float>(), db.as<float>(), dy.as<f16>(), d, rows, d, nullptr);
+    }
+    WDR_HIP(hipDeviceSynchronize());
+    std::vector<f16> h((size_t)rows * d);
+    WDR_HIP(hipMemcpy(h.data(), dy.p, h.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) out[i] = (float)h[i];
     return 0;
   })

@@ -146,12 +146,30 @@ void launch_mel(const MelArgs& a, hipStream_t s) {
   }
 }
 
-__device__ __forceinline__ float mel_norm(float raw, float gmax) {
+// whisper.cpp's clamp (max - 8) and (x + 4) / 4, in double as there
+__device__ __forceinline__ double mel_norm(float raw, float gmax) {
   const double mmax = (double)gmax - 8.0;
   double v = raw;
   float f = raw;
   if (v < mmax) f = (float)mmax;
-  return (float)(((double)f + 4.0) / 4.0);
+  return ((double)f + 4.0) / 4.0;
+}
+
+// The conv1 operand is mel_norm rounded ONCE, double -> f16 (what k_im2col_mel has always stored:
+// the compiler folded an intermediate f32 into the f16 conversion; now it is written that way).
+// whisper.cpp keeps the log-mel as f32 and ggml's im2col rounds that to f16 -- two roundings, one
+// f16 ulp away on the few elements (3 .. 15 of a window measured) whose f32 value lands on an f16
+// tie.  The f32 readback of the window therefore rounds the double TO ODD: f32 carries 13 more
+// bits than f16, so rounding that f32 to f16 (numpy's astype, the host im2col of
+// encode_from_mel_window) gives exactly the f16 the double rounds to, and the debug single-window
+// path feeds conv1 the same bits as every production encode (tests/test_gpu_encoder_kernels.py
+// test_im2col_mel, test_encode_batch).  It is within one f32 ulp of the nearest f32.
+__device__ __forceinline__ float f32_round_to_odd(double d) {
+  float r = (float)d;
+  if ((double)r == d) return r;
+  unsigned b = __float_as_uint(r);
+  if (fabs((double)r) > fabs(d)) b -= 1;   // towards zero (normal range: the window's values are O(1))
+  return __uint_as_float(b | 1u);
 }
 
 __global__ void k_im2col_mel(Im2colMelArgs a) {
@@ -160,17 +178,17 @@ __global__ void k_im2col_mel(Im2colMelArgs a) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int t = (int)(i / a.kp), col = (int)(i % a.kp);
-    float v = 0.f;
+    f16 v = (f16)0.f;
     if (col < a.n_mels * 3) {
       const int ci = col / 3, k = col % 3;
       const int u = t + k - 1;
       if (u >= 0 && u < 3000) {
         const int f = a.seek + u;
         const float raw = f < a.n_fft_frames ? a.mel[(long long)f * a.n_mels + ci] : -10.f;
-        v = mel_norm(raw, gmax);
+        v = (f16)mel_norm(raw, gmax);   // one rounding, double -> f16 (see f32_round_to_odd)
       }
     }
-    a.out[i] = (f16)v;
+    a.out[i] = v;
   }
 }
 
@@ -225,14 +243,15 @@ void launch_im2col_conv2(const f16* x, int d, int nb, f16* out, hipStream_t s) {
   WDR_HIP(hipGetLastError());
 }
 
-// read back the normalised window as f32 [n_mels][3000] (debug / tests)
+// read back the normalised window as f32 [n_mels][3000] (debug / tests), rounded to odd so that its
+// f16 rounding is the conv1 operand k_im2col_mel stores (f32_round_to_odd)
 __global__ void k_mel_window(const float* mel, int n_mels, int n_fft_frames, const int* gmax_ord, int seek, float* out) {
   const float gmax = ord2f(*gmax_ord);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_mels * 3000; i += gridDim.x * blockDim.x) {
     const int ci = i / 3000, u = i % 3000;
     const int f = seek + u;
     const float raw = f < n_fft_frames ? mel[(long long)f * n_mels + ci] : -10.f;
-    out[i] = mel_norm(raw, gmax);
+    out[i] = f32_round_to_odd(mel_norm(raw, gmax));
   }
 }
 

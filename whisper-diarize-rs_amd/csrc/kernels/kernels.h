@@ -112,6 +112,13 @@ struct FlashArgs {
 };
 inline unsigned long long* prof_attach(FlashArgs& a) { return a.ts = prof_slot(); }
 void launch_flash_attn(const FlashArgs& a, int n_batch, hipStream_t s);
+// the encoder's self-attention over stacked windows of T rows (encoder_body; wdr_dbg_attn_batch):
+// Q / K / V interleaved per row as the qkv projection writes them ([T][3d], window b at b * T * 3d),
+// out [T][d] per window (window b at b * T * d), non-causal, scale d_head^-1/2 = 1/8
+inline FlashArgs encoder_flash_args(const f16* qkv, f16* out, int T, int d, int n_head) {
+  const long long bs = (long long)T * 3 * d, obs = (long long)T * d;
+  return FlashArgs{qkv, 3 * d, bs, qkv + d, 3 * d, bs, qkv + 2 * d, 3 * d, bs, out, d, obs, nullptr, T, T, n_head, 0, 1.0f / 8.0f};
+}
 struct DecSelfArgs {
   const f16* q; int ldq;
   const f16* kc; const f16* vc;

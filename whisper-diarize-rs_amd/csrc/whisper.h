@@ -363,6 +363,11 @@ class State {
   void encode_from_mel_window(const float* mel_window);    // [n_mels][3000] normalised, host
   void read_encoder_out(float* out);                       // [1500][d] (ln_post output, f16 -> f32)
   void read_cross_kv(float* out);                          // [1500][L][2][d] of the last encoded window
+  // compute_mel(x, n), then k_im2col_mel at `seek` as encode_window runs it: f16 bits [3000][kp1]
+  void dbg_im2col_mel(const float* x_host, int n, int seek, uint16_t* out);
+  // one unplanned encode-ahead batch of nb (1 .. 4) windows on ring slots 0 .. nb - 1:
+  // enc_out [nb][1500][d], xkv_out [nb][1500][L][2][d]
+  void dbg_encode_batch(const int16_t* const* pcm, const int* n, int nb, float* enc_out, float* xkv_out);
   void decode_logits(const int* toks, int n, float* logits_out);   // prefill from an empty cache
   void dbg_step(const int* toks, int n, float* logits_out);
   void dtw_capture(const int* toks, int n, float* cap_out);        // [n_aheads][n][1500]

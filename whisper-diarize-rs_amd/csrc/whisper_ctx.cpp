@@ -886,6 +886,19 @@ static void slot_mel(Context& ctx, State::Impl& m, State::Impl::Slot& sl, int n,
   launch_mel(a, s);
 }
 
+// the 30-s window at frame `seek` of the slot's log-mel as conv1's operand rows out [3000][kp1]
+static void slot_im2col(State::Impl& m, State::Impl::Slot& sl, int seek, f16* out, hipStream_t s) {
+  Im2colMelArgs ia{sl.mel.as<float>(), m.n_mels, sl.n_fft_frames, sl.gmax.as<int>(), seek, m.kp1, out};
+  launch_im2col_mel(ia, s);
+}
+
+// a segment's int16 PCM through the slot's pinned staging buffer -> its f32 samples (n <= pcm_cap)
+static void slot_load_pcm(State::Impl::Slot& sl, const int16_t* pcm, int n, hipStream_t s) {
+  memcpy(sl.h_pcm, pcm, (size_t)n * 2);
+  WDR_HIP(wdr_memcpy_async(sl.pcm.p, sl.h_pcm, (size_t)n * 2, hipMemcpyHostToDevice, s));
+  launch_i16_to_f32(sl.pcm.as<int16_t>(), n, sl.x.as<float>(), s);
+}
+
 static void slot_reserve_x(State::Impl::Slot& sl, int n) {
   if (n > sl.x_cap) {
     sl.x = DevMem((size_t)std::max(n, 1) * 4);
@@ -959,8 +972,6 @@ static void encoder_body(Context& ctx, State::Impl& m, State::Impl::EncBufs& e, 
   // conv2 (+GELU) + positional -> ex f32 [nb*1500][d]
   proj(s, e.im2col.as<f16>(), 3 * d, md.conv2_w, 3 * d, md.conv2_b, e.ex.p, d, M, d, 3 * d, EPI_F32_GELU_POS,
        md.enc_pos, hp.n_audio_ctx);
-  const float scale = 1.0f / 8.0f;   // d_head^-1/2
-  const long long bs = 1500ll * 3 * d, obs = 1500ll * d;
   // fp8 encoder (BASELINE configs[4]): the four projections of every layer on the MX fp8 GEMM
   // (k_gemm8, twice the f16 MFMA rate); their A operands are written as e4m3 + E8M0 block scales
   // by their producers -- LN1 / LN2 (k_layernorm_f8), fc1's GELU epilogue (EPI_F8_GELU) -- or
@@ -1003,9 +1014,7 @@ static void encoder_body(Context& ctx, State::Impl& m, State::Impl::EncBufs& e, 
       launch_layernorm(e.ex.as<float>(), d, w.ln1_g, w.ln1_b, e.eh.as<f16>(), d, M, d, s);
       proj(s, e.eh.as<f16>(), d, w.w_qkv, d, w.b_qkv, e.eqkv.p, 3 * d, M, 3 * d, d, EPI_F16);
     }
-    FlashArgs fa{e.eqkv.as<f16>(), 3 * d, bs, e.eqkv.as<f16>() + d, 3 * d, bs, e.eqkv.as<f16>() + 2 * d, 3 * d, bs,
-                 e.eatt.as<f16>(), d, obs, nullptr, 1500, 1500, hp.n_audio_head, 0, scale};
-    launch_flash_attn(fa, nb, s);
+    launch_flash_attn(encoder_flash_args(e.eqkv.as<f16>(), e.eatt.as<f16>(), 1500, d, hp.n_audio_head), nb, s);
     if (pl & Context::F8_O) {
       launch_quant_f8(e.eatt.as<f16>(), d, M, d, qa, d, sa, mp, s);
       gemm8(qa, sa, d, w8->o, w.b_o, e.ex.p, d, d, EPI_F32_RESID);
@@ -1056,8 +1065,7 @@ hipStream_t State::encode_window(int seek) {
   // a shared stream: the window's launches issued as one unit (as the encode-ahead batches)
   std::unique_lock<std::mutex> issue_lk;
   if (m.eo.shared) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.eo));
-  Im2colMelArgs ia{sl.mel.as<float>(), m.n_mels, sl.n_fft_frames, sl.gmax.as<int>(), seek, m.kp1, m.e1.im2col.as<f16>()};
-  launch_im2col_mel(ia, s);
+  slot_im2col(m, sl, seek, m.e1.im2col.as<f16>(), s);
   encoder_body(ctx_, m, m.e1, 1, const_cast<f16*>(m.xkv()), s);
   return s;
 }
@@ -1079,15 +1087,19 @@ void State::encode_from_mel_window(const float* w) {
 
 // the current slot's cross K/V as [1500][L*2d] (key-major, K then V of every layer: the
 // reference's per-layer cross-attention K / V projections side by side) from the head-major slot
-void State::read_cross_kv(float* out) {
-  Impl& m = *m_;
-  const int L = ctx_.model.hp.n_text_layer, d = ctx_.model.hp.n_text_state, N = L * 2 * d;
+static void read_slot_kv(const f16* slot, int N, float* out, hipStream_t s) {
   const size_t n = (size_t)XKV_T * N;
   std::vector<f16> h(n);
-  WDR_HIP(wdr_memcpy_async(h.data(), m.xkv(), n * 2, hipMemcpyDeviceToHost, s_));
-  WDR_HIP(hipStreamSynchronize(s_));
+  WDR_HIP(wdr_memcpy_async(h.data(), slot, n * 2, hipMemcpyDeviceToHost, s));
+  WDR_HIP(hipStreamSynchronize(s));
   for (int c = 0; c < N; ++c)
     for (int t = 0; t < XKV_T; ++t) out[(size_t)t * N + c] = (float)h[(size_t)(c >> 6) * XKV_HS + t * 64 + (c & 63)];
+}
+
+void State::read_cross_kv(float* out) {
+  Impl& m = *m_;
+  const int L = ctx_.model.hp.n_text_layer, d = ctx_.model.hp.n_text_state;
+  read_slot_kv(m.xkv(), L * 2 * d, out, s_);
 }
 
 void State::read_encoder_out(float* out) {
@@ -1096,6 +1108,16 @@ void State::read_encoder_out(float* out) {
   WDR_HIP(wdr_memcpy_async(h.data(), m.e1.eh.p, h.size() * 2, hipMemcpyDeviceToHost, s_));
   WDR_HIP(hipStreamSynchronize(s_));
   for (size_t i = 0; i < h.size(); ++i) out[i] = (float)h[i];
+}
+
+// test seam: the conv1 operand rows of the window at frame `seek` of x, computed as encode_window
+// does (compute_mel, then k_im2col_mel into the single-window buffers): raw f16 bits [3000][kp1]
+void State::dbg_im2col_mel(const float* x_host, int n, int seek, uint16_t* out) {
+  Impl& m = *m_;
+  compute_mel(x_host, n);
+  slot_im2col(m, m.slots[m.cur], seek, m.e1.im2col.as<f16>(), s_);
+  WDR_HIP(wdr_memcpy_async(out, m.e1.im2col.p, (size_t)3000 * m.kp1 * 2, hipMemcpyDeviceToHost, s_));
+  WDR_HIP(hipStreamSynchronize(s_));
 }
 
 // ------------------------------------------------------------------ encode-ahead
@@ -1143,6 +1165,49 @@ void State::unplan() {
   times.windows += m.enc_windows.exchange(0);
   times.lang_passes += m.lang_passes.exchange(0);
   times.lang_rows += m.lang_rows.exchange(0);
+}
+
+// test seam: one encode-ahead batch of nb windows (window 0 of nb segments) without a plan -- the
+// front half of top_up_batch per window on ring slot k (PCM -> samples, log-mel, conv1 operand rows
+// k of the batch buffers), then encoder_body over the nb stacked windows into ring slots 0 .. nb - 1
+// -- eagerly on the encode-ahead stream, with no graph, language detection, energy or events.
+// enc_out [nb][1500][d] is the batch buffers' ln_post output, xkv_out [nb][1500][L*2d] every slot as
+// read_cross_kv lays it out.
+void State::dbg_encode_batch(const int16_t* const* pcm, const int* n, int nb, float* enc_out, float* xkv_out) {
+  Impl& m = *m_;
+  WDR_CHECK(nb >= 1 && nb <= kBatch, "dbg_encode_batch: 1.." + std::to_string(kBatch) + " windows");
+  enc_quiesce();
+  es_sync(m);
+  {
+    std::lock_guard<std::mutex> g(m.enc_mu);
+    WDR_CHECK(m.plan.pcm.empty(), "dbg_encode_batch: a plan is active on this state");
+  }
+  flush_dtw();
+  WDR_HIP(hipEventSynchronize(m.ev_dtw));   // a DTW job of this state may still read a ring slot
+  for (int k = 0; k < nb; ++k) {
+    WDR_CHECK(pcm[k] && n[k] >= 1, "dbg_encode_batch: an empty clip");
+    slot_reserve_all(m.slots[k], n[k], m.n_mels);
+  }
+  {
+    std::unique_lock<std::mutex> issue_lk;
+    if (m.es.shared) issue_lk = std::unique_lock<std::mutex>(stream_issue_mutex(m.es));
+    for (int k = 0; k < nb; ++k) {
+      Impl::Slot& sl = m.slots[k];
+      slot_dtw_fence(k, m.es);   // a queued DTW pass may still read the slot
+      slot_load_pcm(sl, pcm[k], n[k], m.es);
+      sl.energy_n = -1;          // the slot's energy is not this segment's
+      slot_mel(ctx_, m, sl, n[k], m.es);
+      slot_im2col(m, sl, 0, m.eb.im2col.as<f16>() + (size_t)k * 3000 * m.kp1, m.es);
+    }
+    encoder_body(ctx_, m, m.eb, nb, m.xkv_ring.as<f16>(), m.es);
+  }
+  std::vector<f16> h((size_t)nb * 1500 * m.d);
+  WDR_HIP(wdr_memcpy_async(h.data(), m.eb.eh.p, h.size() * 2, hipMemcpyDeviceToHost, m.es));
+  WDR_HIP(hipStreamSynchronize(m.es));
+  for (size_t i = 0; i < h.size(); ++i) enc_out[i] = (float)h[i];
+  const int N = m.L * 2 * m.d;
+  for (int k = 0; k < nb; ++k)
+    read_slot_kv(m.xkv_ring.as<f16>() + (size_t)k * m.xkv_slot_elems, N, xkv_out + (size_t)k * XKV_T * N, m.es);
 }
 
 // Segments the encode-ahead stream may run ahead of the decoder (WDR_ENC_AHEAD, kBatch..S;
@@ -1294,7 +1359,8 @@ bool State::top_up_batch(int j) {
   // WDR_ENC_FIRST: windows in the first batch of a plan (A/B: 1 / 2 / 4 measured 491-493 /
   // 495 / 496 xRT on the 1-h bench, so a full batch stays the default); a batch never wraps
   // around the ring (its slots stay contiguous for the cross-K/V GEMM).  Encoder results do not
-  // depend on the batch.
+  // depend on the batch: every window of a 1 .. 4 window batch is bit-identical to its
+  // single-window encode (dbg_encode_batch; tests/test_gpu_encoder_kernels.py).
   // With the encode-ahead thread, a plan's second batch is issued only once its first has been
   // encoded: at the start of a run every chain waits for its first batch, and with all chains'
   // look-ahead batches queued at once the first batches finished late (1-h bench, chain log:
@@ -1332,9 +1398,7 @@ bool State::top_up_batch(int j) {
       slot_reserve_x(sl, nk);
       if (nk > 0) {
         // the staging buffer's previous H2D copy (segment k - S) completed before its decode
-        memcpy(sl.h_pcm, m.plan.pcm[k], (size_t)nk * 2);
-        WDR_HIP(wdr_memcpy_async(sl.pcm.p, sl.h_pcm, (size_t)nk * 2, hipMemcpyHostToDevice, m.es));
-        launch_i16_to_f32(sl.pcm.as<int16_t>(), nk, sl.x.as<float>(), m.es);
+        slot_load_pcm(sl, m.plan.pcm[k], nk, m.es);
         if (nk > sl.energy_cap) {
           std::lock_guard<std::recursive_mutex> g(hip_alloc_mutex());
           if (sl.h_energy) WDR_HIP(hipHostFree(sl.h_energy));
@@ -1347,9 +1411,7 @@ bool State::top_up_batch(int j) {
       }
       sl.energy_n = nk;
       slot_mel(ctx_, m, sl, nk, m.es);
-      Im2colMelArgs ia{sl.mel.as<float>(), m.n_mels, sl.n_fft_frames, sl.gmax.as<int>(), 0, m.kp1,
-                       m.eb.im2col.as<f16>() + (size_t)(k - g0) * 3000 * m.kp1};
-      launch_im2col_mel(ia, m.es);
+      slot_im2col(m, sl, 0, m.eb.im2col.as<f16>() + (size_t)(k - g0) * 3000 * m.kp1, m.es);
     }
     // the batch's encoder + cross-K/V (+ language detection): whisper.cpp's language detection
     // (one SOT pass over window 0, argmax of the language logits) depends on nothing decoded, so

@@ -786,6 +786,68 @@ def dbg_proj_qkv(a, w, bias, row_seq, row_pos, kc, vc, packed=False):
     return q, kb.view(np.float16), vb.view(np.float16)
 
 
+SENTINEL_F16 = 0x7e57        # include/wdr.h WDR_DBG_SENTINEL_F16 / _F32: what an encoder seam's device
+SENTINEL_F32 = 0x7fc07e57    # output holds where the kernel wrote nothing
+
+
+def dbg_proj_enc(a, w, bias, epi: int, pos=None, gemm_ref: bool = False, slot_elems: int = 0) -> np.ndarray:
+    """The encoder-only GEMM epilogues (wdr_dbg_proj_enc): a [M][K], w [N][K] (rounded to f16), bias
+    [N] or None.  epi 4: pos [pos_rows][N] -> float32 [M][N] = gelu(a w^T + bias) + pos[row % pos_rows].
+    epi 6: -> the raw cross-K/V slot images, float16 [M / 1500][slot_elems], SENTINEL_F16 bits where
+    nothing was written.  gemm_ref: the reference tile k_gemm instead of the dispatched kernel."""
+    ab, wb = _h16(a), _h16(w)
+    M, K = ab.shape
+    N = wb.shape[0]
+    if wb.shape != (N, K):
+        raise ValueError("dbg_proj_enc: a [M][K], w [N][K]")
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    p = None if pos is None else np.ascontiguousarray(pos, np.float32)
+    if p is not None and (p.ndim != 2 or p.shape[1] != N):
+        raise ValueError("dbg_proj_enc: pos [pos_rows][N]")
+    if epi == 6:
+        out = np.zeros((max(M // 1500, 1), int(slot_elems)), np.uint16)
+    else:
+        out = np.zeros((M, N), np.float32)
+    L.check(L.load().wdr_dbg_proj_enc(ab.ctypes.data_as(_U16P), wb.ctypes.data_as(_U16P),
+                                      None if b is None else b.ctypes.data_as(_F32P),
+                                      None if p is None else p.ctypes.data_as(_F32P), 0 if p is None else p.shape[0],
+                                      M, N, K, int(epi), 1 if gemm_ref else 0, int(slot_elems),
+                                      out.ctypes.data_as(C.c_void_p)))
+    return out.view(np.float16) if epi == 6 else out
+
+
+def dbg_attn_batch(qkv, n_head: int) -> np.ndarray:
+    """The encoder's batched self-attention launch (wdr_dbg_attn_batch): qkv [nb][T][3 * 64 H]
+    (rounded to f16; Q, K, V of a row side by side) -> float32 [nb][T][64 H]."""
+    qb = _h16(qkv)
+    if qb.ndim != 3 or qb.shape[2] != 3 * 64 * n_head:
+        raise ValueError("dbg_attn_batch: qkv [nb][T][3 * 64 H]")
+    nb, T, _ = qb.shape
+    out = np.zeros((nb, T, 64 * n_head), np.float32)
+    L.check(L.load().wdr_dbg_attn_batch(qb.ctypes.data_as(_U16P), nb, T, n_head, out.ctypes.data_as(_F32P)))
+    return out
+
+
+def dbg_layernorm(x, g, b, d: Optional[int] = None, row_map=None) -> np.ndarray:
+    """k_layernorm alone (wdr_dbg_layernorm): x [rows][ldx] float32 (its first d columns are the
+    row; d defaults to ldx), g / b [d]; row_map [rows] gathers the input rows.  Returns float32
+    [rows][d] (the kernel's f16 output widened)."""
+    xc = np.ascontiguousarray(x, np.float32)
+    rows, ldx = xc.shape
+    d = ldx if d is None else int(d)
+    gc, bc = np.ascontiguousarray(g, np.float32), np.ascontiguousarray(b, np.float32)
+    if gc.shape != (d,) or bc.shape != (d,):
+        raise ValueError("dbg_layernorm: g / b [d]")
+    rm = None if row_map is None else np.ascontiguousarray(row_map, np.int32)
+    if rm is not None and rm.shape != (rows,):
+        raise ValueError("dbg_layernorm: row_map [rows]")
+    out = np.zeros((rows, d), np.float32)
+    L.check(L.load().wdr_dbg_layernorm(xc.ctypes.data_as(_F32P), ldx, gc.ctypes.data_as(_F32P), bc.ctypes.data_as(_F32P),
+                                       rows, d, None if rm is None else rm.ctypes.data_as(_I32P),
+                                       out.ctypes.data_as(_F32P)))
+    return out
+
+
 class WhisperContext:
     """transcribe::create_context (src/transcribe.rs:89-166) + its whisper_state."""
 
@@ -981,6 +1043,31 @@ class WhisperContext:
         out = np.zeros((1500, h["n_text_layer"], 2, h["n_text_state"]), np.float32)
         L.check(self._lib.wdr_dbg_cross_kv(self.h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def im2col_mel(self, x: np.ndarray, seek: int = 0) -> np.ndarray:
+        """conv1's operand rows of the window at frame `seek` of x, as every production encode
+        builds them (wdr_dbg_im2col_mel): float16 [3000][kp], column 3 ci + k of row t = channel ci
+        at window frame t + k - 1."""
+        x = np.ascontiguousarray(x, np.float32)
+        kp = C.c_int32()
+        L.check(self._lib.wdr_dbg_im2col_mel(self.h, None, 0, 0, None, C.byref(kp)))
+        out = np.zeros((3000, kp.value), np.uint16)
+        L.check(self._lib.wdr_dbg_im2col_mel(self.h, x.ctypes.data_as(_F32P), x.size, int(seek),
+                                             out.ctypes.data_as(_U16P), C.byref(kp)))
+        return out.view(np.float16)
+
+    def encode_batch(self, clips):
+        """One encode-ahead batch of len(clips) (1 .. 4) windows, window 0 of each int16 clip
+        (wdr_dbg_encode_batch): (encoder output [nb][1500][d], cross K/V [nb][1500][n_text_layer][2][d])."""
+        pcm = [np.ascontiguousarray(c, np.int16) for c in clips]
+        nb = len(pcm)
+        h = self.hparams
+        ptr = (C.POINTER(C.c_int16) * max(1, nb))(*[p.ctypes.data_as(C.POINTER(C.c_int16)) for p in pcm])
+        n = (C.c_int32 * max(1, nb))(*[p.size for p in pcm])
+        enc = np.zeros((nb, 1500, h["n_audio_state"]), np.float32)
+        xkv = np.zeros((nb, 1500, h["n_text_layer"], 2, h["n_text_state"]), np.float32)
+        L.check(self._lib.wdr_dbg_encode_batch(self.h, ptr, n, nb, enc.ctypes.data_as(_F32P), xkv.ctypes.data_as(_F32P)))
+        return enc, xkv
 
     def decode(self, tokens) -> np.ndarray:
         t = np.ascontiguousarray(tokens, np.int32)

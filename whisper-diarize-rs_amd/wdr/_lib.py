@@ -233,6 +233,12 @@ _SIGS = {
     "wdr_dbg_logits_probs": (C.c_int, [vp, P(f32), i32, P(i32), P(f32), f32, i32, P(f32), P(f32)]),
     "wdr_dbg_kv_rows": (C.c_int, [vp, i32, i32, i32, P(C.c_uint16), P(C.c_uint16)]),
     "wdr_dbg_kv_reorder": (C.c_int, [vp, P(i32), P(i32), i32, i32]),
+    "wdr_dbg_im2col_mel": (C.c_int, [vp, P(f32), sz, i32, P(C.c_uint16), P(i32)]),
+    "wdr_dbg_proj_enc": (C.c_int, [P(C.c_uint16), P(C.c_uint16), P(f32), P(f32), i32, i32, i32, i32, i32, i32, i64,
+                                   vp]),
+    "wdr_dbg_attn_batch": (C.c_int, [P(C.c_uint16), i32, i32, i32, P(f32)]),
+    "wdr_dbg_layernorm": (C.c_int, [P(f32), i32, P(f32), P(f32), i32, i32, P(i32), P(f32)]),
+    "wdr_dbg_encode_batch": (C.c_int, [vp, P(P(C.c_int16)), P(i32), i32, P(f32), P(f32)]),
 }
 
 _lib = None
