@@ -30,6 +30,9 @@
  *   wdr_transcribe_batch / wdr_batch_free many files in one call, each equal to its wdr_transcribe_audio
  *   wdr_run_pipeline_groups              several recordings' segments in one pipeline run (segment groups)
  *   wdr_vad_probs_batch                  wdr_vad_probs of several recordings in one pass
+ *   wdr_diarize_frame_classes_batch      wdr_diarize_frame_classes of several recordings in shared forwards
+ *   wdr_run_pipeline_groups_diarize      segment groups with speakers: an EmbeddingManager per group
+ *   wdr_engine_set_batch_diarize         wdr_transcribe_batch takes enable_diarize, each file as its single call
  * The wdr_dbg_* functions are kernel-level test seams (parity tests call them).
  */
 #ifndef WDR_H
@@ -224,6 +227,19 @@ int wdr_engine_set_audio_convert(wdr_engine* e, int8_t on);
  * enable_diarize == 1 fails with "channel split labels speakers by channel: enable_diarize must
  * not be set" before the file is read. */
 int wdr_engine_set_channel_split(wdr_engine* e, int8_t on);
+/* Diarized batches (an explicit opt-in).  0 (default) = wdr_transcribe_batch refuses enable_diarize
+ * == 1 with the message given there.  1 = it takes it, and (*out)[i].list equals
+ * wdr_transcribe_audio of file i with the same options -- segments, words, times, speaker ids
+ * ("1", "2", .. starting afresh in every file) and detected_lang.  The order of work: both
+ * diarization model paths are resolved as the single call resolves them (a failure fails the
+ * whole call with its message); every file is read (read errors go on the item); the segmentation
+ * windows of all readable files run through shared forwards (wdr_diarize_frame_classes_batch) and
+ * are stitched per file; one wdr_run_pipeline_groups_diarize run with a group per file;
+ * process_segments per file without a VAD mask.  enable_vad is ignored when diarizing, as in the
+ * single call; audio convert composes as without diarization.  With channel split on,
+ * enable_diarize == 1 fails before any file is read with the single call's "channel split labels
+ * speakers by channel: enable_diarize must not be set".  Not in the Rust API. */
+int wdr_engine_set_batch_diarize(wdr_engine* e, int8_t on);
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* opts,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out);
 /* Batch transcription (additive, not in the Rust API): n_files recordings in one call, so that
@@ -236,7 +252,8 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
  * ("audio file doesn't exist", the header errors, ..) and list == NULL; the other files are
  * unaffected.  Model not found, translate_target, cancellation and GPU errors fail the whole call
  * as they fail wdr_transcribe_audio.  enable_diarize == 1 fails before any file is read: "batch
- * transcription does not diarize: enable_diarize must not be set".  n_files == 0 succeeds with
+ * transcription does not diarize: enable_diarize must not be set" (unless the engine opted in:
+ * wdr_engine_set_batch_diarize).  n_files == 0 succeeds with
  * *out == NULL.  new_segment fires in (file, channel, segment) order on the calling thread with
  * the file's index; progress reports finished speech segments over all files.
  * Free *out with wdr_batch_free. */
@@ -330,6 +347,15 @@ void wdr_diarizer_free(wdr_diarizer* d);
  * find_max_index: last max): cls_out[n_windows * 589], n_windows = n / 160000 + 1;
  * logprobs_out (nullable) [n_windows][589][7] */
 int wdr_diarize_frame_classes(wdr_diarizer* d, const int16_t* samples, size_t n, int32_t* cls_out, float* logprobs_out);
+/* the same for B recordings at once: file b contributes the n[b] / 160000 + 1 windows of its own
+ * zero-padded buffer, the windows are stacked in (file, window) order and run through forwards of
+ * up to window_cap windows each (0 = the default, 128; larger values mean 128), so a forward may
+ * start or end inside a file.  cls_out / logprobs_out (nullable) hold the per-file results back to
+ * back, every window bit-identical to wdr_diarize_frame_classes of its file alone.  n[b] == 0 is
+ * legal: one all-zero window, samples[b] is not read.  B <= 0, a NULL samples[b] with n[b] > 0 or
+ * window_cap < 0 is an error before anything is launched */
+int wdr_diarize_frame_classes_batch(wdr_diarizer* d, const int16_t* const* samples, const size_t* n, int32_t B,
+                                    int32_t window_cap, int32_t* cls_out, float* logprobs_out);
 /* pyannote_rs::get_segments: one allocation holding the segments and copies of their samples
  * (slices of the zero-padded buffer); free with wdr_free(*segs_out) */
 int wdr_diarize_get_segments(wdr_diarizer* d, const int16_t* samples, size_t n, wdr_speech_segment** segs_out,
@@ -402,11 +428,22 @@ int wdr_run_pipeline_block(wdr_context* c, const wdr_speech_segment* segs, size_
  * progress counts finished segments over all of them.  out: n_groups lists, each freed with
  * wdr_segment_list_free.  n_groups == 0 needs n_segs == 0 and does nothing.  Speaker embeddings
  * are per pipeline call, so more than one group with opts->enable_diarize == 1 is refused:
- * "segment groups do not diarize: more than one group with diarization on". */
+ * "segment groups do not diarize: more than one group with diarization on"
+ * (wdr_run_pipeline_groups_diarize is the entry point that takes them). */
 int wdr_run_pipeline_groups(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
                             const size_t* group_start, size_t n_groups, const char* const* group_speaker,
                             const wdr_transcribe_options* opts, const wdr_synthetic* syn,
                             const wdr_callbacks* cb, wdr_segment_list** out /* [n_groups] */);
+/* Segment groups with speakers: as wdr_run_pipeline_groups without group_speaker, and with
+ * wdr_run_pipeline's explicit diarize argument -- NULL = no speakers; else group g's speaker ids
+ * are exactly those of its own wdr_run_pipeline call with the same wdr_diarize_options: the
+ * EmbeddingManager (max_speakers, threshold) starts afresh at a group's first segment, while one
+ * embedding worker runs ahead over the segments of all groups (an embedding depends on its
+ * segment's samples only, bit for bit) */
+int wdr_run_pipeline_groups_diarize(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
+                                    const size_t* group_start, size_t n_groups, const wdr_transcribe_options* opts,
+                                    const wdr_diarize_options* diarize, const wdr_synthetic* syn,
+                                    const wdr_callbacks* cb, wdr_segment_list** out /* [n_groups] */);
 void wdr_segment_list_free(wdr_segment_list* l);
 /* decode chains of run_pipeline (greedy decoding): n States decode n contiguous blocks of the
  * speech segments concurrently, their greedy steps batched into one n-row step, with an exact

@@ -128,7 +128,8 @@ SegModel::SegModel(int dev, const std::string& path) : device(dev) {
   for (int l = 0; l < 4; ++l) { w.wih[l] = b + o_wih[l]; w.bih[l] = b + o_bih[l]; w.whh[l] = b + o_whh[l]; w.bhh[l] = b + o_bhh[l]; }
   w.l0w = b + o_l0w; w.l0b = b + o_l0b; w.l1w = b + o_l1w; w.l1b = b + o_l1b; w.cw = b + o_cw; w.cb = b + o_cb;
   const size_t B = kSegBatch;
-  w.pcm = DevMem(B * kWin * 2);
+  // staging image of a forward: the window table, the samples, 8-sample alignment per file
+  w.pcm = DevMem(B * (kWin * 2 + sizeof(SegWin) + 16));
   w.x = DevMem(B * kWin * 4);
   w.col = DevMem(B * 15975 * 251 * 4);
   w.s1 = DevMem(B * 15975 * 80 * 4);
@@ -168,62 +169,66 @@ static void gemm(hipStream_t s, const float* A, int lda, const float* B, int ldb
 }
 
 std::vector<int> SegModel::frame_classes(const int16_t* pcm, size_t n, std::vector<float>* logprobs) {
+  return frame_classes_batch(&pcm, &n, 1, 0, logprobs);
+}
+
+std::vector<int> SegModel::frame_classes_batch(const int16_t* const* pcm, const size_t* n, int B, int window_cap,
+                                               std::vector<float>* logprobs) {
   WDR_HIP(hipSetDevice(device));
   W& w = *w_;
-  const size_t padded = n + (kWin - n % kWin);
-  const int nw = (int)(padded / kWin);
-  std::vector<int> cls((size_t)nw * kFrames);
-  if (logprobs) logprobs->assign((size_t)nw * kFrames * 7, 0.f);
+  const size_t cap = (window_cap <= 0 || window_cap > kSegBatch) ? kSegBatch : window_cap;
+  // windows of the zero-padded files, stacked: file f owns windows [first[f], first[f + 1])
+  std::vector<size_t> first((size_t)std::max(B, 0) + 1, 0);
+  for (int f = 0; f < B; ++f) first[f + 1] = first[f] + n[f] / kWin + 1;
+  const size_t nw = first.back();
+  std::vector<int> cls(nw * kFrames);
+  if (logprobs) logprobs->assign(nw * kFrames * 7, 0.f);
   WDR_HIP(hipEventRecord(e0_, s_));
-  for (int w0 = 0; w0 < nw; w0 += kSegBatch) {
-    const int B = std::min(kSegBatch, nw - w0);
-    // windows of the zero-padded buffer: raw int16 values as f32 (no 1/32768)
-    WDR_HIP(wdr_memset_async(w.pcm.p, 0, (size_t)B * kWin * 2, s_));
-    const size_t s0 = (size_t)w0 * kWin;
-    const size_t avail = s0 < n ? std::min(n - s0, (size_t)B * kWin) : 0;
-    if (avail) WDR_HIP(wdr_memcpy_async(w.pcm.p, pcm + s0, avail * 2, hipMemcpyHostToDevice, s_));
-    launch_i16_scale(w.pcm.as<int16_t>(), (long long)B * kWin, 1.0f, w.x.as<float>(), s_);
-    launch_inorm(w.x.as<float>(), kWin, kWin, 1, B, w.wn_g, w.wn_b, ACT_NONE, s_);
-    // SincNet
-    for (int b = 0; b < B; ++b)
-      launch_im2col_1d(w.x.as<float>() + (size_t)b * kWin, 1, kWin, 1, 251, 10, 1, 0, 15975,
-                       w.col.as<float>() + (size_t)b * 15975 * 251, s_);
-    gemm(s_, w.col.as<float>(), 251, w.sinc, 251, w.s1.as<float>(), 80, B * 15975, 80, 251, nullptr, ACT_ABS);
-    launch_maxpool3(w.s1.as<float>(), 15975ll * 80, 15975, 80, B, w.p1.as<float>(), 5325ll * 80, s_);
-    launch_inorm(w.p1.as<float>(), 5325ll * 80, 5325, 80, B, w.ng[0], w.nb[0], ACT_LRELU, s_);
-    for (int b = 0; b < B; ++b)
-      launch_im2col_1d(w.p1.as<float>() + (size_t)b * 5325 * 80, 80, 5325, 80, 5, 1, 1, 0, 5321,
-                       w.col.as<float>() + (size_t)b * 5321 * 400, s_);
-    gemm(s_, w.col.as<float>(), 400, w.c1w, 400, w.s2.as<float>(), 60, B * 5321, 60, 400, w.c1b, ACT_NONE);
-    launch_maxpool3(w.s2.as<float>(), 5321ll * 60, 5321, 60, B, w.p2.as<float>(), 1773ll * 60, s_);
-    launch_inorm(w.p2.as<float>(), 1773ll * 60, 1773, 60, B, w.ng[1], w.nb[1], ACT_LRELU, s_);
-    for (int b = 0; b < B; ++b)
-      launch_im2col_1d(w.p2.as<float>() + (size_t)b * 1773 * 60, 60, 1773, 60, 5, 1, 1, 0, 1769,
-                       w.col.as<float>() + (size_t)b * 1769 * 300, s_);
-    gemm(s_, w.col.as<float>(), 300, w.c2w, 300, w.s3.as<float>(), 60, B * 1769, 60, 300, w.c2b, ACT_NONE);
-    launch_maxpool3(w.s3.as<float>(), 1769ll * 60, 1769, 60, B, w.p3.as<float>(), (long long)kFrames * 60, s_);
-    launch_inorm(w.p3.as<float>(), (long long)kFrames * 60, kFrames, 60, B, w.ng[2], w.nb[2], ACT_LRELU, s_);
-    // 4 x BiLSTM: input projections of both directions in one GEMM, then the scans
-    const float* in = w.p3.as<float>();
-    int in_dim = 60;
-    float* hb[2] = {w.h0.as<float>(), w.h1.as<float>()};
-    for (int l = 0; l < 4; ++l) {
-      gemm(s_, in, in_dim, w.wih[l], in_dim, w.xg.as<float>(), 1024, B * kFrames, 1024, in_dim, w.bih[l], ACT_NONE);
-      launch_lstm_scan(w.xg.as<float>(), (long long)kFrames * 1024, 1024, kFrames, B, w.whh[l], w.bhh[l], hb[l & 1],
-                       (long long)kFrames * 256, 256, s_);
-      in = hb[l & 1];
-      in_dim = 256;
+  std::vector<char> img;
+  std::vector<SegWin> tab;
+  struct Piece {
+    const int16_t* p;
+    size_t cnt, off;
+  };
+  std::vector<Piece> pieces;
+  int f0 = 0;   // the file of window g0
+  for (size_t g0 = 0; g0 < nw; g0 += cap) {
+    const size_t Bf = std::min(cap, nw - g0);
+    // one staging image, one upload: the window table, then the samples each file has in this
+    // forward's windows, every file's piece starting on a multiple of 8 samples (k_seg_stage's
+    // 16-byte loads); the kernel writes raw int16 values as f32 (no 1/32768) and the
+    // zeros past a file's end
+    while (first[f0 + 1] <= g0) ++f0;
+    tab.assign(Bf, SegWin{0, 0, 0});
+    pieces.clear();
+    size_t ns = 0, g = 0;
+    for (int f = f0; g < Bf; ++f) {
+      const size_t wa = g0 + g - first[f];                                        // file f's windows [wa, wb)
+      const size_t wb = std::min(first[f + 1] - first[f], wa + (Bf - g));
+      const size_t s0 = wa * kWin, s1 = std::min(n[f], wb * kWin);
+      for (size_t wi = wa; wi < wb; ++wi, ++g) {
+        const size_t ws = wi * kWin;
+        if (n[f] > ws) tab[g] = SegWin{(long long)(ns + (ws - s0)), (int)std::min(n[f] - ws, (size_t)kWin), 0};
+      }
+      if (s1 > s0) {
+        pieces.push_back({pcm[f] + s0, s1 - s0, ns});
+        ns += (s1 - s0 + 7) / 8 * 8;
+      }
     }
-    gemm(s_, in, 256, w.l0w, 256, w.la.as<float>(), 128, B * kFrames, 128, 256, w.l0b, ACT_LRELU);
-    gemm(s_, w.la.as<float>(), 128, w.l1w, 128, w.lb.as<float>(), 128, B * kFrames, 128, 128, w.l1b, ACT_LRELU);
-    gemm(s_, w.lb.as<float>(), 128, w.cw, 128, w.z.as<float>(), 7, B * kFrames, 7, 128, w.cb, ACT_NONE);
-    launch_logsoftmax7(w.z.as<float>(), B * kFrames, w.cls.as<int>(), s_);
-    WDR_HIP(wdr_memcpy_async(cls.data() + (size_t)w0 * kFrames, w.cls.p, (size_t)B * kFrames * 4, hipMemcpyDeviceToHost,
-                           s_));
+    const size_t tab_bytes = Bf * sizeof(SegWin);
+    img.resize(tab_bytes + ns * 2);
+    WDR_CHECK(img.size() <= w.pcm.bytes, "segmentation: staging image larger than its buffer");
+    memcpy(img.data(), tab.data(), tab_bytes);
+    for (const Piece& p : pieces) memcpy(img.data() + tab_bytes + p.off * 2, p.p, p.cnt * 2);
+    WDR_HIP(wdr_memcpy_async(w.pcm.p, img.data(), img.size(), hipMemcpyHostToDevice, s_));
+    launch_seg_stage(reinterpret_cast<const int16_t*>(w.pcm.as<char>() + tab_bytes), w.pcm.as<SegWin>(), (int)Bf, kWin,
+                     w.x.as<float>(), s_);
+    forward((int)Bf);
+    WDR_HIP(wdr_memcpy_async(cls.data() + g0 * kFrames, w.cls.p, Bf * kFrames * 4, hipMemcpyDeviceToHost, s_));
     if (logprobs)
-      WDR_HIP(wdr_memcpy_async(logprobs->data() + (size_t)w0 * kFrames * 7, w.z.p, (size_t)B * kFrames * 7 * 4,
-                             hipMemcpyDeviceToHost, s_));
-    WDR_HIP(hipStreamSynchronize(s_));   // host staging of the next batch reuses the buffers
+      WDR_HIP(wdr_memcpy_async(logprobs->data() + g0 * kFrames * 7, w.z.p, Bf * kFrames * 7 * 4, hipMemcpyDeviceToHost,
+                               s_));
+    WDR_HIP(hipStreamSynchronize(s_));   // host staging of the next forward reuses the image and the buffers
   }
   WDR_HIP(hipEventRecord(e1_, s_));
   WDR_HIP(hipStreamSynchronize(s_));
@@ -231,6 +236,41 @@ std::vector<int> SegModel::frame_classes(const int16_t* pcm, size_t n, std::vect
   WDR_HIP(hipEventElapsedTime(&ms, e0_, e1_));
   last_ms = ms;
   return cls;
+}
+
+// One forward over the B staged windows w.x [B][160000]: per window (GEMM rows, k_inorm per (b, c),
+// k_lstm_scan per (window, direction)), so a window's result does not depend on its neighbours.
+void SegModel::forward(int B) {
+  W& w = *w_;
+  launch_inorm(w.x.as<float>(), kWin, kWin, 1, B, w.wn_g, w.wn_b, ACT_NONE, s_);
+  // SincNet
+  launch_im2col_1d(w.x.as<float>(), kWin, 1, kWin, 1, 251, 10, 1, 0, 15975, B, w.col.as<float>(), 15975ll * 251, s_);
+  gemm(s_, w.col.as<float>(), 251, w.sinc, 251, w.s1.as<float>(), 80, B * 15975, 80, 251, nullptr, ACT_ABS);
+  launch_maxpool3(w.s1.as<float>(), 15975ll * 80, 15975, 80, B, w.p1.as<float>(), 5325ll * 80, s_);
+  launch_inorm(w.p1.as<float>(), 5325ll * 80, 5325, 80, B, w.ng[0], w.nb[0], ACT_LRELU, s_);
+  launch_im2col_1d(w.p1.as<float>(), 5325ll * 80, 80, 5325, 80, 5, 1, 1, 0, 5321, B, w.col.as<float>(), 5321ll * 400, s_);
+  gemm(s_, w.col.as<float>(), 400, w.c1w, 400, w.s2.as<float>(), 60, B * 5321, 60, 400, w.c1b, ACT_NONE);
+  launch_maxpool3(w.s2.as<float>(), 5321ll * 60, 5321, 60, B, w.p2.as<float>(), 1773ll * 60, s_);
+  launch_inorm(w.p2.as<float>(), 1773ll * 60, 1773, 60, B, w.ng[1], w.nb[1], ACT_LRELU, s_);
+  launch_im2col_1d(w.p2.as<float>(), 1773ll * 60, 60, 1773, 60, 5, 1, 1, 0, 1769, B, w.col.as<float>(), 1769ll * 300, s_);
+  gemm(s_, w.col.as<float>(), 300, w.c2w, 300, w.s3.as<float>(), 60, B * 1769, 60, 300, w.c2b, ACT_NONE);
+  launch_maxpool3(w.s3.as<float>(), 1769ll * 60, 1769, 60, B, w.p3.as<float>(), (long long)kFrames * 60, s_);
+  launch_inorm(w.p3.as<float>(), (long long)kFrames * 60, kFrames, 60, B, w.ng[2], w.nb[2], ACT_LRELU, s_);
+  // 4 x BiLSTM: input projections of both directions in one GEMM, then the scans
+  const float* in = w.p3.as<float>();
+  int in_dim = 60;
+  float* hb[2] = {w.h0.as<float>(), w.h1.as<float>()};
+  for (int l = 0; l < 4; ++l) {
+    gemm(s_, in, in_dim, w.wih[l], in_dim, w.xg.as<float>(), 1024, B * kFrames, 1024, in_dim, w.bih[l], ACT_NONE);
+    launch_lstm_scan(w.xg.as<float>(), (long long)kFrames * 1024, 1024, kFrames, B, w.whh[l], w.bhh[l], hb[l & 1],
+                     (long long)kFrames * 256, 256, s_);
+    in = hb[l & 1];
+    in_dim = 256;
+  }
+  gemm(s_, in, 256, w.l0w, 256, w.la.as<float>(), 128, B * kFrames, 128, 256, w.l0b, ACT_LRELU);
+  gemm(s_, w.la.as<float>(), 128, w.l1w, 128, w.lb.as<float>(), 128, B * kFrames, 128, 128, w.l1b, ACT_LRELU);
+  gemm(s_, w.lb.as<float>(), 128, w.cw, 128, w.z.as<float>(), 7, B * kFrames, 7, 128, w.cb, ACT_NONE);
+  launch_logsoftmax7(w.z.as<float>(), B * kFrames, w.cls.as<int>(), s_);
 }
 
 // pyannote_rs::get_segments: frame k of the file sits at sample 721 + 270 k (continuing across

@@ -30,6 +30,12 @@ class SegModel {
   // per-window frame classes (argmax, last max on ties) of the zero-padded file:
   // [n_windows][589]; optionally the log-probabilities [n_windows][589][7]
   std::vector<int> frame_classes(const int16_t* pcm, size_t n, std::vector<float>* logprobs = nullptr);
+  // frame_classes of B recordings in shared forwards: file b's n[b] / 160000 + 1 windows stacked in
+  // (file, window) order and run window_cap at a time (0, or more than a forward holds: kSegBatch;
+  // a forward may start or end inside a file).  The results lie back to back per file, each window
+  // bit-identical to frame_classes of its file alone.  n[b] == 0 is legal (pcm[b] is not read).
+  std::vector<int> frame_classes_batch(const int16_t* const* pcm, const size_t* n, int B, int window_cap = 0,
+                                       std::vector<float>* logprobs = nullptr);
   // pyannote_rs::get_segments (src/engine.rs:117-122)
   std::vector<DiarSegment> get_segments(const int16_t* pcm, size_t n);
   double last_ms = 0.0;
@@ -40,6 +46,7 @@ class SegModel {
   W* w_ = nullptr;
   hipStream_t s_ = nullptr;
   hipEvent_t e0_ = nullptr, e1_ = nullptr;
+  void forward(int B);   // the staged windows x [B][160000] -> classes and log-probabilities
 };
 
 class CamModel {

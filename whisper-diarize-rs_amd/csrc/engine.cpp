@@ -384,6 +384,7 @@ struct wdr_engine {
   bool audio_convert = false;   // wdr_engine_set_audio_convert: any supported WAV, converted on the GPU
   std::unique_ptr<AudioConverter> conv;   // its streams, staging and per-rate tables (made on first use)
   bool channel_split = false;   // wdr_engine_set_channel_split: every channel transcribed on its own, speaker = channel
+  bool batch_diarize = false;   // wdr_engine_set_batch_diarize: wdr_transcribe_batch takes enable_diarize
 };
 
 // src/vad.rs:6-85 on top of the GPU VAD: probabilities -> whisper.cpp segments (cs) -> the
@@ -480,6 +481,33 @@ static std::string find_cached_file(const std::string& cache_dir, const std::str
 // ggml-<model>.bin from ggerganov/whisper.cpp (src/model_manager.rs:148-162)
 static std::string find_model_file(const std::string& cache_dir, const std::string& model) {
   return find_cached_file(cache_dir, "models--ggerganov--whisper.cpp", "ggml-" + model + ".bin");
+}
+
+// a model file from the config, else the cache; absent -> synthetic (opt-in) or an error
+static std::string engine_model_file(const wdr_engine* e, const std::string& cfg_path, const std::string& hub,
+                                     const std::string& file, const char* what) {
+  if (!cfg_path.empty()) {
+    if (!file_exists(cfg_path.c_str())) throw std::runtime_error(std::string(what) + " file doesn't exist: " + cfg_path);
+    return cfg_path;
+  }
+  const std::string f = find_cached_file(e->cache_dir, hub, file);
+  if (f.empty() && !e->syn_set) throw std::runtime_error(std::string(what) + " file doesn't exist");
+  return f;
+}
+// src/engine.rs:89-111: the diarization model paths from the config (both given) or the cache, and
+// the engine's segmentation model made from the first of them
+static void engine_diarize_models(wdr_engine* e, std::string* seg_path, std::string* emb_path) {
+  const bool both = !e->seg_path.empty() && !e->emb_path.empty();
+  *seg_path = engine_model_file(e, both ? e->seg_path : "", "", "segmentation-3.0.onnx", "segmentation model");
+  *emb_path = engine_model_file(e, both ? e->emb_path : "", "", "wespeaker_en_voxceleb_CAM++.onnx", "embedding model");
+}
+static SegModel& engine_seg_model(wdr_engine* e, int dev, const std::string& seg_path) {
+  if (!e->seg || e->seg_loaded != seg_path) {
+    e->seg.reset();
+    e->seg = std::make_unique<SegModel>(dev, seg_path);
+    e->seg_loaded = seg_path;
+  }
+  return *e->seg;
 }
 
 // src/transcribe.rs:89-166.  model_path: a whisper.cpp ggml file (hparams, mel filters, vocabulary and weights from it;
@@ -1101,6 +1129,9 @@ struct RngCarry {
 // the prompt chain, decoder 0's RNG, the overlap clip, the detected language and the speech index
 // restart at its first segment, while all groups share the decode chains.  One group is the
 // reference's pipeline.  group_speaker (nullable, entries nullable): a fixed speaker label per group.
+// dopts with several groups: the speaker manager restarts at a group's first segment as well, while
+// one embedding worker runs ahead over all segments (CamModel::embed_batch is exact per utterance,
+// so its batches may span groups).
 struct GroupLang {
   std::string lang;
   bool has = false;
@@ -1112,15 +1143,19 @@ static std::vector<std::vector<Seg>> run_pipeline_groups(
     const std::vector<const char*>* group_speaker = nullptr, size_t* cur_group = nullptr) {
   // cur_group (nullable): set to a segment's group before its new_segment callback fires
   const size_t n_groups = gs.size() - 1;
-  if (dopts && n_groups > 1)
-    throw std::runtime_error("segment groups do not diarize: more than one group with diarization on");
   if (carry && n_groups > 1) throw std::runtime_error("segment groups: the RNG carry is single-group");
   std::vector<size_t> grp(segs.size(), 0);   // group of segment i
   for (size_t g = 0; g < n_groups; ++g)
     for (size_t i = gs[g]; i < gs[g + 1]; ++i) grp[i] = g;
   const bool diarize = dopts != nullptr && !raw;
   const float dthr = dopts ? dopts->threshold : 0.5f;
-  SpeakerManager speakers(dopts ? dopts->max_speakers : UINT64_MAX);
+  // diarized groups: an EmbeddingManager per group, made at the group's first segment (the
+  // reference makes one per pipeline call, src/transcribe.rs:339-345), so a group's speaker ids are
+  // those of its own call; the embeddings themselves depend on a segment's PCM only
+  std::vector<std::unique_ptr<SpeakerManager>> speakers(n_groups);
+  if (diarize && group_speaker)
+    for (const char* fixed : *group_speaker)
+      if (fixed) throw std::runtime_error("segment groups: a group has a fixed speaker and diarization on");
   if (diarize) {
     // EmbeddingExtractor::new(&diarize_options.embedding_model_path) (src/transcribe.rs:343)
     const std::string path = dopts->embedding_model_path ? dopts->embedding_model_path : "";
@@ -1277,7 +1312,9 @@ static std::vector<std::vector<Seg>> run_pipeline_groups(
           have_emb = true;
         }
         s.has_speaker = true;
-        s.speaker = speakers.assign(emb, 512, dthr);
+        std::unique_ptr<SpeakerManager>& mgr = speakers[grp[i]];
+        if (!mgr) mgr = std::make_unique<SpeakerManager>(dopts->max_speakers);
+        s.speaker = mgr->assign(emb, 512, dthr);
       } else if (fixed_speaker) {   // channel split: the caller knows who speaks
         s.has_speaker = true;
         s.speaker = fixed_speaker;
@@ -1607,6 +1644,14 @@ int wdr_engine_set_channel_split(wdr_engine* e, int8_t on) {
   })
 }
 
+int wdr_engine_set_batch_diarize(wdr_engine* e, int8_t on) {
+  WDR_GUARD({
+    WDR_USE(eng, e);
+    e->batch_diarize = on != 0;
+    return 0;
+  })
+}
+
 int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transcribe_options* o,
                          const wdr_formatting_overrides* fmt, const wdr_callbacks* cb, wdr_segment_list** out) {
   WDR_GUARD({
@@ -1638,16 +1683,8 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
     bool have_mask = false;
     const bool vad = !o || o->enable_vad == 1;   // `if let Some(true) = options.enable_vad` (src/engine.rs:123)
     const int dev = e->cfg.has_gpu_device ? e->cfg.gpu_device : 0;
-    // a model file from the config, else the cache; absent -> synthetic (opt-in) or an error
-    auto resolve = [&](const std::string& cfg_path, const std::string& hub, const std::string& file,
-                       const char* what) -> std::string {
-      if (!cfg_path.empty()) {
-        if (!file_exists(cfg_path.c_str())) throw std::runtime_error(std::string(what) + " file doesn't exist: " + cfg_path);
-        return cfg_path;
-      }
-      const std::string f = find_cached_file(e->cache_dir, hub, file);
-      if (f.empty() && !e->syn_set) throw std::runtime_error(std::string(what) + " file doesn't exist");
-      return f;
+    auto resolve = [&](const std::string& cfg_path, const std::string& hub, const std::string& file, const char* what) {
+      return engine_model_file(e, cfg_path, hub, file, what);
     };
     if (e->channel_split) {
       // each channel is what a mono file of it would be -- its own segmentation, its
@@ -1736,15 +1773,8 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
       // src/engine.rs:89-122: model paths from the config (both given) or the cache, then
       // pyannote segmentation -> SpeechSegments
       diarize = true;
-      const bool both = !e->seg_path.empty() && !e->emb_path.empty();
-      seg_path = resolve(both ? e->seg_path : "", "", "segmentation-3.0.onnx", "segmentation model");
-      emb_path = resolve(both ? e->emb_path : "", "", "wespeaker_en_voxceleb_CAM++.onnx", "embedding model");
-      if (!e->seg || e->seg_loaded != seg_path) {
-        e->seg.reset();
-        e->seg = std::make_unique<SegModel>(dev, seg_path);
-        e->seg_loaded = seg_path;
-      }
-      const std::vector<DiarSegment> ds = e->seg->get_segments(pcm.data(), pcm.size());
+      engine_diarize_models(e, &seg_path, &emb_path);
+      const std::vector<DiarSegment> ds = engine_seg_model(e, dev, seg_path).get_segments(pcm.data(), pcm.size());
       dpad.assign(pcm.begin(), pcm.end());
       dpad.resize(pcm.size() + (160000 - pcm.size() % 160000), 0);
       for (const DiarSegment& d : ds) segs.push_back({d.start, d.end, dpad.data() + d.start_idx, d.end_idx - d.start_idx});
@@ -1787,6 +1817,10 @@ int wdr_transcribe_audio(wdr_engine* e, const char* audio_path, const wdr_transc
 // files' channels; one grouped pipeline run, a group per file (per channel under channel split);
 // process_segments per file / channel with its own mask and language preset -- each step what
 // wdr_transcribe_audio does for one file, so the lists are equal to its lists.
+// Diarized (wdr_engine_set_batch_diarize, enable_diarize): the model paths first; after the reads one
+// SegModel::frame_classes_batch over all readable files in place of the VAD pass, diar_stitch per
+// file into its own zero-padded copy, the grouped run with a speaker manager per group, and
+// process_segments without a mask -- again the single call's steps, file by file.
 int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n_files,
                          const wdr_transcribe_options* o, const wdr_formatting_overrides* fmt,
                          const wdr_batch_callbacks* cb, wdr_batch_item** out) {
@@ -1794,8 +1828,11 @@ int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n
     WDR_USE(eng, e);
     if (!out) return fail("batch transcription: out is NULL");
     *out = nullptr;
-    if (o && o->enable_diarize == 1)
+    const bool diarize = o && o->enable_diarize == 1;
+    if (diarize && !e->batch_diarize)
       return fail("batch transcription does not diarize: enable_diarize must not be set");
+    if (diarize && e->channel_split)
+      return fail("channel split labels speakers by channel: enable_diarize must not be set");
     if (n_files == 0) return 0;
     if (!audio_paths) return fail("batch transcription: audio_paths is NULL");
     const std::string model = (o && o->model) ? o->model : "base";
@@ -1807,8 +1844,10 @@ int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n
     }
     if (o && o->translate_target && !(o->whisper_to_english == 1))
       return fail("translate_target: network translation is out of scope for libwdr");
-    const bool vad = !o || o->enable_vad == 1;
+    const bool vad = !diarize && (!o || o->enable_vad == 1);   // the diarize branch comes first (src/engine.rs:89-123)
     const int dev = e->cfg.has_gpu_device ? e->cfg.gpu_device : 0;
+    std::string seg_path, emb_path;
+    if (diarize) engine_diarize_models(e, &seg_path, &emb_path);
     struct File {
       std::string err;
       bool ok = false;
@@ -1822,6 +1861,7 @@ int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n
       const int16_t* x = nullptr;
       size_t n = 0;
       std::vector<std::pair<double, double>> mask;
+      std::vector<int16_t> dpad;   // diarized: owns the samples of the pyannote segments (they index the padded buffer)
       std::vector<wdr_speech_segment> segs;
       long long group = -1;   // its segment group; -1: no pipeline run (channel split, no speech)
       std::string label;      // channel split: the speaker
@@ -1858,7 +1898,27 @@ int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n
         seqs.push_back(std::move(s));
       }
     }
-    if (vad && !seqs.empty()) {
+    if (diarize && !seqs.empty()) {
+      // src/engine.rs:112-122 for every file: the windows of all files through shared forwards
+      std::vector<const int16_t*> px(seqs.size());
+      std::vector<size_t> pn(seqs.size());
+      for (size_t s = 0; s < seqs.size(); ++s) {
+        px[s] = seqs[s].x;
+        pn[s] = seqs[s].n;
+      }
+      const std::vector<int> cls =
+          engine_seg_model(e, dev, seg_path).frame_classes_batch(px.data(), pn.data(), (int)seqs.size());
+      size_t w0 = 0;
+      for (Seq& s : seqs) {
+        const size_t nw = s.n / 160000 + 1;
+        const std::vector<int> own(cls.begin() + w0 * 589, cls.begin() + (w0 + nw) * 589);
+        w0 += nw;
+        s.dpad.assign(s.x, s.x + s.n);
+        s.dpad.resize(nw * 160000, 0);
+        for (const DiarSegment& d : diar_stitch(own, s.n))
+          s.segs.push_back({d.start, d.end, s.dpad.data() + d.start_idx, d.end_idx - d.start_idx});
+      }
+    } else if (vad && !seqs.empty()) {
       std::string vp;
       if (!e->vad_path.empty()) {
         if (!file_exists(e->vad_path.c_str())) return fail("VAD model file doesn't exist: " + e->vad_path);
@@ -1932,8 +1992,9 @@ int wdr_transcribe_batch(wdr_engine* e, const char* const* audio_paths, size_t n
       const double t = now_s();
       c->st->times = StageTimes{};
       c->cs = wdr_context::ChainStats{};
-      res = run_pipeline_groups(c, segs, gs, o, nullptr, e->syn, cb ? &wcb : nullptr, &langs, false, nullptr, &spk,
-                                &ad.group);
+      const wdr_diarize_options dopts = diarize_options(o, seg_path.c_str(), emb_path.c_str());
+      res = run_pipeline_groups(c, segs, gs, o, diarize ? &dopts : nullptr, e->syn, cb ? &wcb : nullptr, &langs, false,
+                                nullptr, &spk, &ad.group);
       c->st->times.glue = now_s() - t;
     }
     // per file: the preset of the detected (else requested) language + overrides, process_segments
@@ -2114,6 +2175,24 @@ int wdr_diarize_frame_classes(wdr_diarizer* d, const int16_t* samples, size_t n,
     WDR_USE(dia, d);
     std::vector<float> lp;
     const std::vector<int> cls = d->S().frame_classes(samples, n, logprobs_out ? &lp : nullptr);
+    for (size_t i = 0; i < cls.size(); ++i) cls_out[i] = cls[i];
+    if (logprobs_out && !lp.empty()) memcpy(logprobs_out, lp.data(), lp.size() * 4);
+    return 0;
+  })
+}
+
+int wdr_diarize_frame_classes_batch(wdr_diarizer* d, const int16_t* const* samples, const size_t* n, int32_t B,
+                                    int32_t window_cap, int32_t* cls_out, float* logprobs_out) {
+  WDR_GUARD({
+    WDR_USE(dia, d);
+    // on the host, before the model (and with it the device) is touched
+    if (B <= 0) return fail("frame classes batch: the file count must be positive");
+    if (window_cap < 0) return fail("frame classes batch: negative window_cap");
+    if (!samples || !n || !cls_out) return fail("frame classes batch: NULL arrays");
+    for (int32_t b = 0; b < B; ++b)
+      if (n[b] && !samples[b]) return fail("frame classes batch: a file with samples is NULL");
+    std::vector<float> lp;
+    const std::vector<int> cls = d->S().frame_classes_batch(samples, n, B, window_cap, logprobs_out ? &lp : nullptr);
     for (size_t i = 0; i < cls.size(); ++i) cls_out[i] = cls[i];
     if (logprobs_out && !lp.empty()) memcpy(logprobs_out, lp.data(), lp.size() * 4);
     return 0;
@@ -2539,6 +2618,28 @@ int wdr_run_pipeline_groups(wdr_context* c, const wdr_speech_segment* segs, size
     c->cs = wdr_context::ChainStats{};
     std::vector<std::vector<Seg>> res =
         run_pipeline_groups(c, v, gs, o, nullptr, syn_of(syn), cb, &langs, false, nullptr, &spk);
+    c->st->times.glue = now_s() - t;
+    for (size_t g = 0; g < n_groups; ++g) out[g] = to_list(res[g], langs[g].has ? &langs[g].lang : nullptr);
+    return 0;
+  })
+}
+
+int wdr_run_pipeline_groups_diarize(wdr_context* c, const wdr_speech_segment* segs, size_t n_segs,
+                                    const size_t* group_start, size_t n_groups, const wdr_transcribe_options* o,
+                                    const wdr_diarize_options* dopts, const wdr_synthetic* syn, const wdr_callbacks* cb,
+                                    wdr_segment_list** out) {
+  WDR_GUARD({
+    WDR_USE(ctx, c);
+    const std::vector<size_t> gs = group_bounds(group_start, n_groups, n_segs);   // before any GPU work
+    if (n_groups == 0) return 0;
+    if (n_segs && !segs) return fail("segment groups: segs is NULL");
+    if (!out) return fail("segment groups: out is NULL");
+    std::vector<wdr_speech_segment> v(segs, segs + n_segs);
+    std::vector<GroupLang> langs;
+    const double t = now_s();
+    c->st->times = StageTimes{};
+    c->cs = wdr_context::ChainStats{};
+    std::vector<std::vector<Seg>> res = run_pipeline_groups(c, v, gs, o, dopts, syn_of(syn), cb, &langs);
     c->st->times.glue = now_s() - t;
     for (size_t g = 0; g < n_groups; ++g) out[g] = to_list(res[g], langs[g].has ? &langs[g].lang : nullptr);
     return 0;

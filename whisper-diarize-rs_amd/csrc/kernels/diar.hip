@@ -10,7 +10,9 @@
 //
 //  k_gemm32        C = act(affine(A' . B^T) [+ C]), A' = optional per-column affine+ReLU of A
 //                  (the BN-ReLU that precedes every CAM linear), 64x64x16 tiles, 4x4 per thread.
-//  k_im2col_1d     k-tap / strided / dilated conv rows over [T][C] (c-major taps as torch).
+//  k_seg_stage     int16 PCM of several recordings -> the segmentation windows [W][160000] f32.
+//  k_im2col_1d     k-tap / strided / dilated conv rows over [T][C] (c-major taps as torch), one
+//                  window per blockIdx.y.
 //  k_im2col_2d     3x3 (or 1x1) conv over [T][F][C] with a frequency stride (FCM front-end).
 //  k_maxpool3 / k_inorm   maxpool-3, InstanceNorm(affine) + LeakyReLU (SincNet; double sums).
 //  k_lstm_scan     one workgroup per (window, direction): the 4 gate rows of a hidden unit in
@@ -195,9 +197,13 @@ void launch_gemm32(const Gemm32Args& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- im2col
-// col[t][c*k + j] = X[t*stride + j*dil - pad][c]  (zero outside [0, T))
-__global__ void k_im2col_1d(const float* X, int ldx, int T, int C, int k, int stride, int dil, int pad, int To,
-                            float* col) {
+// col[b][t][c*k + j] = X[b][t*stride + j*dil - pad][c]  (zero outside [0, T)); window b = blockIdx.y,
+// its input at X + b * xbs and its rows at col + b * cbs (64-bit: 128 windows of 15975 x 251 columns
+// pass 2^32 bytes); the index within a window is what the one-window kernel computed
+__global__ void k_im2col_1d(const float* Xall, long long xbs, int ldx, int T, int C, int k, int stride, int dil, int pad,
+                            int To, float* colall, long long cbs) {
+  const float* X = Xall + (long long)blockIdx.y * xbs;
+  float* col = colall + (long long)blockIdx.y * cbs;
   const long long total = (long long)To * C * k;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int t = (int)(i / (C * k));
@@ -208,12 +214,13 @@ __global__ void k_im2col_1d(const float* X, int ldx, int T, int C, int k, int st
   }
 }
 
-void launch_im2col_1d(const float* X, int ldx, int T, int C, int k, int stride, int dil, int pad, int To, float* col,
-                      hipStream_t s) {
+void launch_im2col_1d(const float* X, long long xbs, int ldx, int T, int C, int k, int stride, int dil, int pad, int To,
+                      int B, float* col, long long cbs, hipStream_t s) {
   const long long total = (long long)To * C * k;
-  if (total <= 0) return;
+  if (total <= 0 || B <= 0) return;
+  WDR_CHECK(B <= 65535, "im2col 1d: too many windows");
   const int grid = (int)std::min<long long>(cdiv((int)std::min<long long>(total, 1ll << 30), 256), 8192);
-  WDR_KLAUNCH(k_im2col_1d, dim3(grid), dim3(256), 0, s, X, ldx, T, C, k, stride, dil, pad, To, col);
+  WDR_KLAUNCH(k_im2col_1d, dim3(grid, B), dim3(256), 0, s, X, xbs, ldx, T, C, k, stride, dil, pad, To, col, cbs);
   WDR_HIP(hipGetLastError());
 }
 
@@ -762,6 +769,40 @@ void launch_i16_scale(const int16_t* in, long long n, float scale, float* out, h
   if (n <= 0) return;
   WDR_KLAUNCH(k_i16_scale, dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)), dim3(256), 0, s, in, n,
                      scale, out);
+  WDR_HIP(hipGetLastError());
+}
+
+// Segmentation windows of several recordings: x[w][i] = i < tab[w].valid ? (float)pcm[tab[w].src + i]
+// : 0 for i < win -- the raw int16 value as f32, what k_i16_scale at scale 1 writes, and the zero
+// padding of a recording's last window (the next recording's first window follows it, so no
+// memset + one contiguous copy can lay the windows out).  Window w = blockIdx.y; 8 samples per
+// thread: one 16-byte load (every src is a multiple of 8 samples, SegModel stages it so) and two
+// 16-byte stores (win % 8 == 0), element-wise across a window's valid end.
+typedef short short8 __attribute__((ext_vector_type(8)));
+__global__ __launch_bounds__(256) void k_seg_stage(const int16_t* __restrict__ pcm, const SegWin* __restrict__ tab,
+                                                   int win, float* __restrict__ x) {
+  const SegWin t = tab[blockIdx.y];
+  const int16_t* src = pcm + t.src;
+  float* dst = x + (long long)blockIdx.y * win;
+  for (int i = (blockIdx.x * 256 + threadIdx.x) * 8; i < win; i += gridDim.x * 256 * 8) {
+    float v[8];
+    if (i + 8 <= t.valid) {
+      const short8 q = *reinterpret_cast<const short8*>(src + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (float)q[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (i + j < t.valid) ? (float)src[i + j] : 0.f;
+    }
+    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(dst + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+}
+
+void launch_seg_stage(const int16_t* pcm, const SegWin* tab, int W, int win, float* x, hipStream_t s) {
+  if (W <= 0 || win <= 0) return;
+  WDR_CHECK(win % 8 == 0 && W <= 65535, "segmentation staging: window size / count");
+  WDR_KLAUNCH(k_seg_stage, dim3(cdiv(win / 8, 256), W), dim3(256), 0, s, pcm, tab, win, x);
   WDR_HIP(hipGetLastError());
 }
 

@@ -220,8 +220,9 @@ struct Gemm32Args {
 };
 void launch_gemm32(const Gemm32Args& a, hipStream_t s);
 void set_gemm32_mfma(bool on);   // the f32 MFMA kernel (default) or the VALU one
-void launch_im2col_1d(const float* X, int ldx, int T, int C, int k, int stride, int dil, int pad, int To, float* col,
-                      hipStream_t s);
+// B windows in one launch: window b reads X + b * xbs and writes col + b * cbs
+void launch_im2col_1d(const float* X, long long xbs, int ldx, int T, int C, int k, int stride, int dil, int pad, int To,
+                      int B, float* col, long long cbs, hipStream_t s);
 void launch_im2col_2d(const float* X, int T, int F, int C, int kf, int kt, int sf, int Fo, float* col, hipStream_t s);
 void launch_maxpool3(const float* x, long long bs, int T, int C, int B, float* y, long long ybs, hipStream_t s);
 void launch_inorm(float* y, long long bs, int T, int C, int B, const float* g, const float* beta, int act,
@@ -234,6 +235,14 @@ void launch_fbank(const float* x, int T, const float* povey, const float* cos_t,
 void launch_colstats(float* x, int ld, int T, int C, int mode, float* out, hipStream_t s);
 void launch_cam_context(const float* h, int ldh, int T, int C, float* out, hipStream_t s);
 void launch_i16_scale(const int16_t* in, long long n, float scale, float* out, hipStream_t s);
+// segmentation staging: window w of x [W][win] f32 = pcm[tab[w].src .. + tab[w].valid) as f32, then
+// zeros; src in samples, a multiple of 8 (16-byte loads), 0 <= valid <= win, win % 8 == 0
+struct SegWin {
+  long long src;
+  int valid;
+  int pad_;
+};
+void launch_seg_stage(const int16_t* pcm, const SegWin* tab, int W, int win, float* x, hipStream_t s);
 void launch_cam_gate(const float* y, int ldy, const float* m, int T, int G, float* out, int ldo, hipStream_t s);
 // batched CAM++: utterance b owns rows [off[b], off[b] + len[b]) (device arrays, off[B] = total)
 struct SegRows {

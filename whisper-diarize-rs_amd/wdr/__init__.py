@@ -593,6 +593,29 @@ class Diarizer:
         cls = cls.reshape(nw, 589)
         return (cls, lp.reshape(nw, 589, 7)) if logprobs else cls
 
+    def frame_classes_batch(self, sequences, logprobs: bool = False, window_cap: int = 0):
+        """frame_classes() of several recordings in shared forwards (wdr_diarize_frame_classes_batch:
+        all files' windows stacked, up to window_cap -- 0 = the default, 128 -- per forward).  Returns
+        one result per sequence, bit-identical to frame_classes() of it; empty sequences are legal."""
+        smp = [np.ascontiguousarray(x, np.int16).reshape(-1) for x in sequences]
+        B = len(smp)
+        ptrs = (C.POINTER(C.c_int16) * max(B, 1))(*[x.ctypes.data_as(C.POINTER(C.c_int16)) for x in smp])
+        ns = (C.c_size_t * max(B, 1))(*[x.size for x in smp])
+        nw = [x.size // 160000 + 1 for x in smp]
+        tot = max(1, sum(nw))
+        cls = np.zeros(tot * 589, np.int32)
+        lp = np.zeros(tot * 589 * 7, np.float32) if logprobs else None
+        L.check(self._lib.wdr_diarize_frame_classes_batch(self.h, ptrs, ns, B, window_cap,
+                                                          cls.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          lp.ctypes.data_as(C.POINTER(C.c_float)) if logprobs else None))
+        ends = np.cumsum([0] + nw)
+        out = []
+        for b in range(B):
+            c = cls[ends[b] * 589:ends[b + 1] * 589].reshape(nw[b], 589).copy()
+            out.append((c, lp[ends[b] * 589 * 7:ends[b + 1] * 589 * 7].reshape(nw[b], 589, 7).copy())
+                       if logprobs else c)
+        return out
+
     def get_segments(self, samples: np.ndarray, materialize: bool = True):
         """pyannote_rs::get_segments (wdr_diarize_get_segments: the segments and their samples are
         made in libwdr).  materialize=False returns (start, end) pairs without copying every
@@ -906,13 +929,18 @@ class WhisperContext:
 
     def run_pipeline_groups(self, groups, options: TranscribeOptions, speakers=None,
                             callbacks: Optional[Callbacks] = None, synthetic: Optional[Synthetic] = None,
-                            with_index: bool = False, group_start=None):
+                            with_index: bool = False, group_start=None,
+                            diarize: Optional[DiarizeOptions] = None):
         """Several independent recordings' speech segments in one pipeline run
         (wdr_run_pipeline_groups): groups is a list of lists of SpeechSegment; the result is one
         (segments, detected_lang) [+ speech index] per group, each equal to run_pipeline(group, ...)
         without diarization, while the decode chains are shared by all groups.  speakers: an
         optional fixed speaker_id per group (entries may be None).  group_start (test seam): pass
-        the raw group_start array with groups as one flat list of segments."""
+        the raw group_start array with groups as one flat list of segments.  diarize: speakers are
+        assigned per group (wdr_run_pipeline_groups_diarize), each group equal to
+        run_pipeline(group, ..., diarize_options=diarize); not together with speakers."""
+        if diarize is not None and speakers is not None:
+            raise ValueError("a group's speakers are fixed or diarized, not both")
         keep = _Keep()
         if group_start is None:
             flat = [s for g in groups for s in g]
@@ -932,8 +960,14 @@ class WhisperContext:
             spk = (C.c_char_p * max(1, G))(*[_s(x) for x in speakers])
         out = (C.POINTER(L.SegmentList) * max(1, G))()
         syn = _syn(synthetic or self.synthetic)
-        L.check(self._lib.wdr_run_pipeline_groups(self.h, arr, len(flat), gs, G, spk, _opts(options, keep),
-                                                  C.byref(syn) if syn else None, _callbacks(callbacks, keep), out))
+        if diarize is not None:
+            d = _dopts(diarize, keep)
+            L.check(self._lib.wdr_run_pipeline_groups_diarize(self.h, arr, len(flat), gs, G, _opts(options, keep),
+                                                              C.byref(d), C.byref(syn) if syn else None,
+                                                              _callbacks(callbacks, keep), out))
+        else:
+            L.check(self._lib.wdr_run_pipeline_groups(self.h, arr, len(flat), gs, G, spk, _opts(options, keep),
+                                                      C.byref(syn) if syn else None, _callbacks(callbacks, keep), out))
         return [_segments(out[g], with_index) for g in range(G)]
 
     def run_pipeline_raw(self, speech_segments, options: TranscribeOptions, synthetic: Optional[Synthetic] = None):
@@ -1186,7 +1220,7 @@ class Engine:
     """Engine (src/engine.rs:52-217)."""
 
     def __init__(self, cfg: Optional[EngineConfig] = None, synthetic: Optional[Synthetic] = None,
-                 audio_convert: bool = False, channel_split: bool = False):
+                 audio_convert: bool = False, channel_split: bool = False, batch_diarize: bool = False):
         cfg = cfg or EngineConfig()
         lib = L.load()
         self._lib = lib
@@ -1205,6 +1239,14 @@ class Engine:
             self.set_audio_convert(True)
         if channel_split:
             self.set_channel_split(True)
+        if batch_diarize:
+            self.set_batch_diarize(True)
+
+    def set_batch_diarize(self, on: bool):
+        """True: transcribe_batch takes enable_diarize, every file equal to its transcribe_audio
+        (speaker ids start afresh in every file); False (default): it refuses it.  Not in the
+        reference."""
+        L.check(self._lib.wdr_engine_set_batch_diarize(self.h, 1 if on else 0))
 
     def set_audio_convert(self, on: bool):
         """True: transcribe_audio takes any WAV read_audio takes, converted on the engine's GPU;
@@ -1233,7 +1275,8 @@ class Engine:
         """Many recordings in one call (wdr_transcribe_batch): result i holds what
         transcribe_audio(paths[i], options, overrides) returns on this engine (and the detected
         language), the decode chains and the VAD pass shared by all files.  A file that cannot be
-        read gets its error instead; the others are unaffected.  enable_diarize is refused."""
+        read gets its error instead; the others are unaffected.  enable_diarize is refused unless
+        the engine was made with batch_diarize (set_batch_diarize)."""
         keep = _Keep()
         n = len(paths)
         arr = (C.c_char_p * max(1, n))(*[_s(p) for p in paths])

@@ -145,6 +145,7 @@ _SIGS = {
     "wdr_read_audio_channels": (C.c_int, [cstr, i8, i32, P(P(C.c_int16)), P(sz), P(i32)]),
     "wdr_dbg_audio_split": (C.c_int, [P(C.c_uint8), u64, i32, i32, i32, u64, i32, P(P(C.c_int16)), P(sz), P(f64)]),
     "wdr_engine_set_channel_split": (C.c_int, [vp, i8]),
+    "wdr_engine_set_batch_diarize": (C.c_int, [vp, i8]),
     "wdr_dbg_resample_table": (C.c_int, [i32, P(i32), P(i32), P(i32), P(P(f32))]),
     "wdr_dbg_model_file": (C.c_int, [i32, cstr, P(C.c_void_p), P(P(f32)), P(sz)]),
     "wdr_process_segments": (C.c_int, [P(Segment), sz, cstr, P(FormattingOverrides), i8, P(f64), sz,
@@ -161,6 +162,7 @@ _SIGS = {
     "wdr_diarizer_create": (C.c_int, [cstr, cstr, i8, i32, P(vp)]),
     "wdr_diarizer_free": (None, [vp]),
     "wdr_diarize_frame_classes": (C.c_int, [vp, P(C.c_int16), sz, P(i32), P(f32)]),
+    "wdr_diarize_frame_classes_batch": (C.c_int, [vp, P(P(C.c_int16)), P(sz), i32, i32, P(i32), P(f32)]),
     "wdr_diarize_get_segments": (C.c_int, [vp, P(C.c_int16), sz, P(P(SpeechSegment)), P(sz)]),
     "wdr_diarize_segments_from_classes": (C.c_int, [P(i32), sz, P(C.c_int16), sz, P(P(SpeechSegment)), P(sz)]),
     "wdr_diarize_fbank": (C.c_int, [vp, P(C.c_int16), sz, P(f32), P(sz)]),
@@ -178,6 +180,8 @@ _SIGS = {
                                    P(Callbacks), P(P(SegmentList))]),
     "wdr_run_pipeline_groups": (C.c_int, [vp, P(SpeechSegment), sz, P(sz), sz, P(cstr), P(TranscribeOptions),
                                           P(Synthetic), P(Callbacks), P(P(SegmentList))]),
+    "wdr_run_pipeline_groups_diarize": (C.c_int, [vp, P(SpeechSegment), sz, P(sz), sz, P(TranscribeOptions),
+                                                  P(DiarizeOptions), P(Synthetic), P(Callbacks), P(P(SegmentList))]),
     "wdr_run_pipeline_block": (C.c_int, [vp, P(SpeechSegment), sz, P(TranscribeOptions), P(Synthetic), cstr, P(i8),
                                          P(C.c_void_p), P(P(SegmentList))]),
     "wdr_segment_list_free": (None, [P(SegmentList)]),
